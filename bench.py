@@ -7,7 +7,11 @@ all-reduce when N>1] -> Adam on the Gaussians and the MLP. Workload: synth-100k 
 100k Gaussians, 800x800, blender deformation network (timenet on), SH degree 3, synthetic
 (random-init weights, random target image). Inputs are resident in HBM before timing starts.
 
-Run: python bench.py [--gpus N --steps K --warmup W]. N>1: one rank per GPU over RCCL. Under
+Run: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]. A plain run sets up,
+warms up, times the K steps and prints the result line; --dump-outputs DIR also writes what the last
+timed step computed as DIR/<name>.npy (dump_outputs; that step then runs from the starting parameters, so
+two runs agree to rounding); --full adds the CPU baseline leg (cpu_baseline) to
+the line. N>1: one rank per GPU over RCCL. Under
 torch.distributed.run (WORLD_SIZE set) each process is one rank; invoked directly with --gpus N > 1 the
 parent makes no GPU call and starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` as
 a child process, waits for it and exits with its return code (launcher_cmd). Rank 0 prints ONE JSON line
@@ -95,7 +99,13 @@ def parse(argv=None):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--n", type=int, default=100_000)
     ap.add_argument("--res", type=int, default=800)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline leg (cpu_baseline, "
+                         "SURVEY.md 8d's CPU column; ~23 CPU steps of the same workload)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed (loss, render package, "
+                         "parameter gradients) as DIR/<name>.npy (float32; see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline leg")
     ap.add_argument("--cpu-warmup", type=int, default=3)
     ap.add_argument("--cpu-steps", type=int, default=20, help="timed CPU steps (median; SURVEY.md 8d: 3 + 20)")
     ap.add_argument("--no-adam", action="store_true", help="time only the reference's span (fwd+bwd)")
@@ -252,6 +262,27 @@ def cpu_baseline(N, res, steps, warmup=3):
                 median_s=float(np.median(times)), min_s=float(np.min(times)))
 
 
+DUMP_BUDGET_BYTES = 56 << 20  # --dump-outputs writes at most this much (whole arrays when they fit)
+DUMP_WHOLE_BYTES = 1 << 20    # arrays up to this size are never sampled
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: tensor} as out_dir/<name>.npy in float32. When the arrays together exceed
+    DUMP_BUDGET_BYTES, every array above DUMP_WHOLE_BYTES is written as a fixed sample of its flattened
+    elements instead: sorted indices drawn without replacement by numpy's default_rng(0), the same
+    fraction of each such array, so the same arguments always give the same elements."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: v.detach().to(device="cpu", dtype=torch.float32).contiguous().numpy() for k, v in arrays.items()}
+    small = sum(a.nbytes for a in host.values() if a.nbytes <= DUMP_WHOLE_BYTES)
+    big = sum(a.nbytes for a in host.values() if a.nbytes > DUMP_WHOLE_BYTES)
+    frac = 1.0 if small + big <= DUMP_BUDGET_BYTES else max(DUMP_BUDGET_BYTES - small, 0) / big
+    for name, a in host.items():
+        if frac < 1.0 and a.nbytes > DUMP_WHOLE_BYTES:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, int(a.size * frac), replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     # a launched rank takes the parent's arguments from DGS_BENCH_ARGV (launcher_cmd)
     args = parse(json.loads(os.environ[ARGV_ENV]) if "WORLD_SIZE" in os.environ and ARGV_ENV in os.environ else None)
@@ -314,7 +345,25 @@ def main():
         lambda: list(deform.deform.parameters()))
     agreement = OverflowAgreement()
 
-    state = {"it": 3000, "P": 0, "redos": 0, "host_fb": 0.0, "host_opt": 0.0}
+    state = {"it": 3000, "P": 0, "redos": 0, "host_fb": 0.0, "host_opt": 0.0, "last": None}
+    gparams = {"xyz": gaussians._xyz, "features_dc": gaussians._features_dc, "features_rest": gaussians._features_rest,
+               "scaling": gaussians._scaling, "rotation": gaussians._rotation, "opacity": gaussians._opacity}
+    mparams = {"deform_" + k: v for k, v in deform.deform.named_parameters()}
+    # --dump-outputs: the float atomics of the backward add in arrival order, and Adam (eps 1e-15) turns
+    # that last-bit noise of a near-zero gradient into whole learning-rate steps, so after a few steps
+    # two runs of one build hold parameters that differ by per cents of their range. The dumped step
+    # therefore starts from the parameters every run starts from: they are copied here and written back
+    # (one multi-tensor copy, inside the timed region) just before the last timed step, whose loss, render
+    # package and gradients depend on the parameters, the camera and the target only
+    all_params = list(gparams.values()) + list(mparams.values())
+    start_params = [p.detach().clone() for p in all_params] if args.dump_outputs else None
+
+    def restore_start_params():
+        with torch.no_grad():
+            torch._foreach_copy_(all_params, start_params)
+
+    if start_params is not None:
+        restore_start_params()  # same values; the copy kernel is loaded here, not inside the timed region
 
     def step(k):
         cam = cams[k % len(cams)]
@@ -325,6 +374,8 @@ def main():
         loss, pkg, redone = train_step(gaussians, deform, cam, gts[k % len(cams)], pipe, bg, six,
                                        deferred_count=not SYNC_COUNT, allreduce=allreduce, agreement=agreement)
         state["redos"] += int(redone)
+        if args.dump_outputs:  # what the step hands its caller (references only: no copy, no GPU work)
+            state["last"] = (loss, pkg, [p.grad for p in gparams.values()], [p.grad for p in mparams.values()])
         h1 = time.perf_counter()
         if not args.no_adam:
             optimizer_step(gaussians, deform, state["it"])
@@ -353,6 +404,8 @@ def main():
     wait0 = lib.dgs_debug_count_wait_ns(waits)
     t0 = time.perf_counter()
     for k in range(args.steps):
+        if start_params is not None and k == args.steps - 1:
+            restore_start_params()  # the last step computes from the run's starting parameters (see above)
         step(k)
     torch.cuda.synchronize()
     t_local = time.perf_counter() - t0  # this rank's own steps, before waiting for the others
@@ -361,6 +414,17 @@ def main():
     elapsed = time.perf_counter() - t0
     wait_ms = (lib.dgs_debug_count_wait_ns(waits) - wait0) / 1e6
     lib.dgs_timing_enable(0)
+    if args.dump_outputs and rank == 0:
+        # the last timed step's results, before anything else runs: the loss and render package train_step
+        # returned and the gradients it left on the parameters (computed from the starting parameters)
+        loss, pkg, ggrads, mgrads = state["last"]
+        out = {"loss": loss.reshape(1), "render": pkg["render"], "depth": pkg["depth"], "radii": pkg["radii"],
+               "visibility_filter": pkg["visibility_filter"], "viewspace_grad": pkg["viewspace_points"].grad,
+               "viewspace_grad_densify": pkg["viewspace_points_densify"].grad}
+        for names, grads in ((gparams, ggrads), (mparams, mgrads)):
+            for k, g in zip(names, grads):
+                out["grad_" + k] = g
+        dump_outputs(args.dump_outputs, {k: v for k, v in out.items() if v is not None})
     el = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     # per rank: its own timed span, the wait for the slowest rank at the closing barrier (imbalance
     # plus collective waits the stream dependencies pushed to the end), the host's pair-count wait and
@@ -485,7 +549,7 @@ def main():
         "dist": {"world_size": world, "backend": dist.get_backend() if world > 1 else None,
                  "ranks": ranks_info},
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         try:
             result["cpu_baseline"] = cpu_baseline(N, R, args.cpu_steps, args.cpu_warmup)
         except Exception as e:  # report, never hide

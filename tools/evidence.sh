@@ -41,7 +41,7 @@ for p in $PARTS; do
       run 300 $O/smoke.txt python -c "import __graft_entry__ as g; g.smoke()"
       tail -1 $O/smoke.txt ;;
     bench)
-      run 400 $O/bench.jsonl python bench.py
+      run 400 $O/bench.jsonl python bench.py --full
       tail -c 600 $O/bench.jsonl ;;
     configs)
       : > $O/configs.jsonl
