@@ -35,6 +35,7 @@
 
 #include "radix.h"
 #include "raster_kernels.h"
+#include "render.h"
 
 namespace dgs {
 
@@ -140,7 +141,10 @@ __device__ __forceinline__ void sh_stage_out(const float *s_sh, float *dsh, floa
     put(drest, SH_ROW - 3, 3);
 }
 
-template <bool STAGE>
+// FWD (forward-only rendering, dgs_render_frames): no backward accumulators are zeroed and neither clamped
+// nor visible is written (acc, clamped, visible are null); every value binning and the blend read (radii
+// included: the binning kernels take the tile rectangle from it) is computed by the same instructions
+template <bool STAGE, bool FWD = false>
 __global__ __launch_bounds__(256) void k_preprocess(
     int P, int D, int M, const float *__restrict__ means3D, const float *__restrict__ scales, float mod,
     const float *__restrict__ rots, const float *__restrict__ cov_pre, const float *__restrict__ opac,
@@ -178,9 +182,10 @@ __global__ __launch_bounds__(256) void k_preprocess(
     if (!live) return;
     // zero this Gaussian's backward accumulator row (the blend backward adds into it): no memset
     // launch in the backward
-    acc[3 * i] = acc[3 * i + 1] = acc[3 * i + 2] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (!FWD) acc[3 * i] = acc[3 * i + 1] = acc[3 * i + 2] = make_float4(0.f, 0.f, 0.f, 0.f);
     radii[i] = 0;
-    if (visible) visible[i] = 0;  // render()'s visibility_filter (radii > 0), when asked for
+    if constexpr (!FWD)
+        if (visible) visible[i] = 0;  // render()'s visibility_filter (radii > 0), when asked for
     tiles[i] = 0;
     dkey[i] = 0xffffffffu;  // culled: sorts last, emits no pairs
     gid[i] = (uint32_t)i;
@@ -248,12 +253,13 @@ __global__ __launch_bounds__(256) void k_preprocess(
         rgb = make_float3(r[0], r[1], r[2]);
     }
     radii[i] = rad;
-    if (visible) visible[i] = rad > 0;
+    if constexpr (!FWD)
+        if (visible) visible[i] = rad > 0;
     xy[i] = make_float2(px, py);
     conic_o[i] = make_float4(con.x, con.y, con.z, op);
     rgbd[i] = make_float4(rgb.x, rgb.y, rgb.z, pv.z);
     tiles[i] = (uint32_t)area;
-    clamped[i] = cl;
+    if constexpr (!FWD) clamped[i] = cl;
     dkey[i] = __float_as_uint(pv.z);  // depth > 0.2: float bits order as the values
 }
 
@@ -1052,6 +1058,157 @@ __global__ __launch_bounds__(256) void k_blend_fwd(const uint2 *__restrict__ ran
         out_color[2 * HW + pid] = C2 + T * bg[2];
         out_depth[pid] = Dd;
     }
+}
+
+// Forward-only blend (dgs_render_frames): k_blend_fwd<false>'s staging, cull, padded batches, predicates and
+// stop, instruction for instruction, so T, C and depth are bitwise its values; what differs is the
+// bookkeeping. No last-contributor tracking (no s_pos in LDS, no per-batch map), no final_T / n_contrib, and
+// the epilogue writes only what the caller asked for, from registers: float CHW colour / depth, 1 - T, the
+// quantised HWC bytes and the frame's depth maximum.
+//   rgb8: trunc(255 * clamp(c, 0, 1)) per channel. With pack8 (W % 4 == 0 and a 4-byte aligned frame, so
+//   every tile row segment starts on a word and holds whole words) the tile's 16 x 48 bytes are assembled
+//   in LDS and stored as dwords (192 per tile instead of 768 byte stores); otherwise byte stores.
+//   dmax: max of the frame's depth as the float's bit pattern (depth is a sum of non-negative terms, so
+//   unsigned order is float order): a wave reduction, then one atomicMax per workgroup.
+__device__ __forceinline__ uint32_t to8b(float c) { return (uint32_t)(255.f * fminf(fmaxf(c, 0.f), 1.f)); }
+
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k_blend_img(const uint2 *__restrict__ ranges, const uint32_t *__restrict__ vals,
+                                                   uint32_t cap, int W, int H, int gx, const float2 *__restrict__ xy,
+                                                   const float4 *__restrict__ conic_o, const float4 *__restrict__ rgbd,
+                                                   const float *bg, float *__restrict__ out_color,
+                                                   float *__restrict__ out_depth, float *__restrict__ out_alpha,
+                                                   uint8_t *__restrict__ out_rgb8, int pack8,
+                                                   uint32_t *__restrict__ dmax) {
+    __shared__ float2 s_xy[TILE_PIX];
+    __shared__ float4 s_co[TILE_PIX];
+    __shared__ float4 s_cd[TILE_PIX];
+    __shared__ uint32_t s_wcnt[TILE_PIX / 64];
+    __shared__ uint32_t s_px[TILE_Y * TILE_X * 3 / 4];  // the tile's HWC bytes (pack8)
+    __shared__ uint32_t s_wmax[TILE_PIX / 64];
+    const int tile = blockIdx.x;
+    const int tid = threadIdx.x;
+    const float tx0 = (float)((tile % gx) * TILE_X), ty0 = (float)((tile / gx) * TILE_Y);
+    const int2 tp = tile_pixel(tid);
+    const int px = (tile % gx) * TILE_X + tp.x;
+    const int py = (tile / gx) * TILE_Y + tp.y;
+    const bool inside = px < W && py < H;
+    const float pfx = (float)px, pfy = (float)py;
+    uint2 range = ranges[tile];
+    range.x = min(range.x, cap);  // a speculative launch under capacity (the frame is redone at the exact size)
+    range.y = min(range.y, cap);
+    const int todo_total = (int)(range.y - range.x);
+    const int rounds = div_up(todo_total, TILE_PIX);
+    bool done = !inside;
+    float T = 1.f, C0 = 0.f, C1 = 0.f, C2 = 0.f, Dd = 0.f;
+    for (int r = 0; r < rounds; r++) {
+        if (__syncthreads_count(done) == TILE_PIX) break;
+        int prog = r * TILE_PIX + tid;
+        bool keep = false;
+        uint32_t id = 0;
+        float2 gl;
+        float4 cl;
+        if ((int)range.x + prog < (int)range.y) {
+            id = vals[range.x + prog];
+            gl = xy[id];
+            cl = conic_o[id];
+            keep = tile_reach(gl, cl, tx0, ty0);
+        }
+        const int2 sl = compact_slot(keep, tid, s_wcnt);
+        if (keep) {
+            s_xy[sl.x] = gl;
+            s_co[sl.x] = conic_q(cl);
+            s_cd[sl.x] = rgbd[id];
+        }
+        const int n = sl.y, n4 = (sl.y + 3) & ~3;  // padded with inert entries, as k_blend_fwd
+        if (tid >= n && tid < n4) {
+            s_xy[tid] = make_float2(0.f, 0.f);
+            s_co[tid] = make_float4(0.f, 0.f, 0.f, 0.f);
+            s_cd[tid] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        __syncthreads();
+        for (int j0 = 0; j0 < n4; j0 += 4) {
+            if (__ballot(!done) == 0ull) break;
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const int j = j0 + u;
+                const float2 g = s_xy[j];
+                const float4 q = s_co[j];
+                const float4 cd = s_cd[j];
+                const float dx = g.x - pfx, dy = g.y - pfy;
+                const float power = q_power(q, dx, dy);
+                const float alpha = fminf(0.99f, q.w * __builtin_amdgcn_exp2f(power));
+                const float testT = T * (1.f - alpha);
+                bool use = !done && !(power > 0.f) && !(alpha < 1.f / 255.f);
+                const bool stop = use && testT < 0.0001f;
+                done = done || stop;
+                use = use && !stop;
+                const float w = use ? alpha * T : 0.f;
+                C0 += cd.x * w;
+                C1 += cd.y * w;
+                C2 += cd.z * w;
+                Dd += cd.w * w;
+                T = use ? testT : T;
+            }
+        }
+    }
+    const float c0 = C0 + T * bg[0], c1 = C1 + T * bg[1], c2 = C2 + T * bg[2];
+    if (inside) {
+        const int pid = py * W + px;
+        const int HW = H * W;
+        if (out_color) {
+            out_color[pid] = c0;
+            out_color[HW + pid] = c1;
+            out_color[2 * HW + pid] = c2;
+        }
+        if (out_depth) out_depth[pid] = Dd;
+        if (out_alpha) out_alpha[pid] = 1.f - T;
+    }
+    if (out_rgb8) {
+        if (pack8) {
+            // (no barrier needed before: s_px is not touched by the blend loop)
+            uint8_t *b = reinterpret_cast<uint8_t *>(s_px) + (tp.y * TILE_X + tp.x) * 3;
+            b[0] = (uint8_t)to8b(c0);
+            b[1] = (uint8_t)to8b(c1);
+            b[2] = (uint8_t)to8b(c2);
+            __syncthreads();
+            // row y of the tile: nw words (3 bytes x the row's pixels inside the image, a multiple of 4)
+            const int tx = (tile % gx) * TILE_X, ty = (tile / gx) * TILE_Y;
+            const int nw = 3 * min(TILE_X, W - tx) / 4;
+            const int y = tid / 12, k = tid - 12 * y;
+            if (tid < TILE_Y * 12 && ty + y < H && k < nw)
+                reinterpret_cast<uint32_t *>(out_rgb8 + ((size_t)(ty + y) * W + tx) * 3)[k] = s_px[y * 12 + k];
+        } else if (inside) {
+            uint8_t *b = out_rgb8 + ((size_t)py * W + px) * 3;
+            b[0] = (uint8_t)to8b(c0);
+            b[1] = (uint8_t)to8b(c1);
+            b[2] = (uint8_t)to8b(c2);
+        }
+    }
+    if (dmax) {
+        uint32_t m = inside ? __float_as_uint(Dd) : 0u;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
+        if ((tid & 63) == 0) s_wmax[tid >> 6] = m;
+        __syncthreads();
+        if (tid == 0) atomicMax(dmax, max(max(s_wmax[0], s_wmax[1]), max(s_wmax[2], s_wmax[3])));
+    }
+}
+
+// depth8 of one frame once its maximum is known (dmax: k_blend_img's word, read on the device, so the
+// host never sees it): trunc(255 * clamp(depth / (max + 1e-5), 0, 1)). 4 pixels per thread, one dword
+// store when pack8 (HW % 4 == 0 and an aligned frame), else bytes.
+__global__ __launch_bounds__(256) void k_depth8(int HW, const float *__restrict__ depth, const uint32_t *__restrict__ dmax,
+                                                uint8_t *__restrict__ out, int pack8) {
+    const float den = __uint_as_float(dmax[0]) + 1e-5f;
+    const int i = 4 * (blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= HW) return;
+    if (pack8) {
+        const float4 d = *reinterpret_cast<const float4 *>(depth + i);
+        *reinterpret_cast<uint32_t *>(out + i) =
+            to8b(d.x / den) | to8b(d.y / den) << 8 | to8b(d.z / den) << 16 | to8b(d.w / den) << 24;
+        return;
+    }
+    for (int j = i; j < min(i + 4, HW); j++) out[j] = (uint8_t)to8b(depth[j] / den);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2501,8 +2658,8 @@ static int det_layout(dgs_raster_ctx *c, int cap, uint32_t **tile_end, float **s
     return DGS_OK;
 }
 
-static int bin_and_blend(dgs_raster_ctx *c, int cap, int P, int device, hipStream_t stream, bool dbg, float *out_color,
-                         float *out_depth) {
+// The tile lists (c->ranges, c->vals) for `cap` pairs: shared by the training forward and dgs_render_frames
+static int bin_lists(dgs_raster_ctx *c, int cap, int P, int device, hipStream_t stream, bool dbg) {
     const int T = c->gx * c->gy;
     if (c->rect_mode) {
         // tile sort: the lists, then 8 + 4 (+ 4: the deterministic mode's copy) bytes of scratch per pair for
@@ -2543,6 +2700,13 @@ static int bin_and_blend(dgs_raster_ctx *c, int cap, int P, int device, hipStrea
         DGS_HIP_CHECK(hipMemsetAsync(c->ranges, 0, 8ull * T, stream));
         c->vals = nullptr;
     }
+    return DGS_OK;
+}
+
+static int bin_and_blend(dgs_raster_ctx *c, int cap, int P, int device, hipStream_t stream, bool dbg, float *out_color,
+                         float *out_depth) {
+    const int T = c->gx * c->gy;
+    if (int rc = bin_lists(c, cap, P, device, stream, dbg)) return rc;
     float4 *ckpt = nullptr, *cfin = nullptr;
     uint32_t *todo = nullptr;
     if (c->seg_ok) {
@@ -3013,6 +3177,270 @@ extern "C" long long dgs_debug_binning_redos(void) {
     std::lock_guard<std::mutex> lk(g_cap_mu);
     return g_redos;
 }
+
+// ================================================================================================
+// dgs_render_frames (render.hip): the forward-only rasterizer of one frame on a per-device workspace
+// ================================================================================================
+// The workspace reuses dgs_raster_ctx as the container of the geometry / binning buffers and their carved
+// views (so bin_lists and the count wait are the training forward's own), but it never enters the
+// context pool and nothing of the backward's lives in it: acc, ckb, segq, det stay unallocated, img
+// holds the tile ranges only, clamped / final_T / n_contrib are null.
+namespace dgs {
+struct RenderWs {
+    std::mutex mu;  // held for the duration of a call
+    dgs_raster_ctx c;
+    DevBuf dev;                    // [depth maxima (F words) | dummy count word | depth scratch (H W floats)]
+    uint32_t *h_counts = nullptr;  // mapped + coherent host array, one pair count per frame
+    uint32_t *d_counts = nullptr;
+    int counts_cap = 0;
+    std::vector<int> caps;         // the capacity every frame was binned with
+    std::vector<char> observed;    // the frame's count already went to pair_cap_observe (a synchronous first frame)
+    int F = 0, last = -1;          // last: the last frame whose count goes to its host slot
+    uint32_t *dmax = nullptr, *dummy = nullptr;
+    float *depth_scratch = nullptr;
+    bool used = false;
+};
+namespace {
+std::mutex g_rws_mu;
+std::map<int, RenderWs *> g_rws;
+}  // namespace
+
+int render_ws_acquire(int F, int P, int H, int W, bool need_depth, hipStream_t stream, RenderWs **out) {
+    int device = 0;
+    DGS_HIP_CHECK(hipGetDevice(&device));
+    RenderWs *ws = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(g_rws_mu);
+        RenderWs *&slot = g_rws[device];
+        if (!slot) {
+            slot = new RenderWs();
+            slot->c.device = device;
+        }
+        ws = slot;
+    }
+    ws->mu.lock();
+    auto fail = [&](int rc) {
+        ws->mu.unlock();
+        return rc;
+    };
+    dgs_raster_ctx *c = &ws->c;
+    if (ws->used && c->last_stream != stream) {  // order this stream after the previous call's work
+        if (!c->released && hipEventCreateWithFlags(&c->released, hipEventDisableTiming) != hipSuccess) {
+            set_error("dgs_render_frames: hipEventCreateWithFlags failed");
+            return fail(DGS_ERR_HIP);
+        }
+        if (hipEventRecord(c->released, c->last_stream) != hipSuccess || hipStreamWaitEvent(stream, c->released, 0) != hipSuccess) {
+            set_error("dgs_render_frames: could not order the stream after the workspace's previous user");
+            return fail(DGS_ERR_HIP);
+        }
+    }
+    ws->used = true;
+    c->last_stream = stream;
+    if (F > ws->counts_cap) {
+        // (the previous array has no writer in flight: every call, a failed one included, waits for the last
+        // count it enqueued before it releases the workspace, and redone frames write theirs to the
+        // device-side dummy word)
+        if (ws->h_counts) (void)hipHostFree(ws->h_counts);
+        ws->h_counts = ws->d_counts = nullptr;
+        ws->counts_cap = 0;
+        const int n = F + F / 2 + 16;
+        if (hipHostMalloc((void **)&ws->h_counts, 4ull * n, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess ||
+            hipHostGetDevicePointer((void **)&ws->d_counts, ws->h_counts, 0) != hipSuccess) {
+            set_error("dgs_render_frames: could not allocate the mapped pair-count array");
+            return fail(DGS_ERR_OOM);
+        }
+        ws->counts_cap = n;
+    }
+    for (int f = 0; f < F; f++) ((volatile uint32_t *)ws->h_counts)[f] = COUNT_PENDING;
+    ws->F = F;
+    ws->last = -1;
+    ws->caps.assign((size_t)F, 0);
+    ws->observed.assign((size_t)F, 0);
+    const size_t o_dummy = 4ull * F, o_depth = align_up(o_dummy + 4);
+    if (int rc = ws->dev.ensure(o_depth + (need_depth ? 4ull * H * W : 0) + 256)) return fail(rc);
+    ws->dmax = (uint32_t *)ws->dev.p;
+    ws->dummy = ws->dmax + F;
+    ws->depth_scratch = need_depth ? (float *)((char *)ws->dev.p + o_depth) : nullptr;
+    if (hipMemsetAsync(ws->dmax, 0, 4ull * F + 4, stream) != hipSuccess) {
+        set_error("dgs_render_frames: hipMemsetAsync failed");
+        return fail(DGS_ERR_HIP);
+    }
+    if (!c->count_ev && hipEventCreateWithFlags(&c->count_ev, hipEventDisableTiming) != hipSuccess) {
+        set_error("dgs_render_frames: hipEventCreateWithFlags failed");
+        return fail(DGS_ERR_HIP);
+    }
+    (void)P;
+    *out = ws;
+    return DGS_OK;
+}
+
+void render_ws_release(RenderWs *ws, hipStream_t stream) {
+    ws->c.last_stream = stream;
+    ws->mu.unlock();
+}
+
+int render_frame_count(const RenderWs *ws, int f) { return (int)((volatile uint32_t *)ws->h_counts)[f]; }
+int render_frame_cap(const RenderWs *ws, int f) { return ws->caps[(size_t)f]; }
+void render_observe_count(const RenderWs *ws, int f, int nr) {
+    if (!ws->observed[(size_t)f]) pair_cap_observe(ws->c.device, nr);
+}
+
+int render_wait_counts(RenderWs *ws, hipStream_t stream) {
+    if (ws->last < 0) return DGS_OK;  // no frame wrote a count (P = 0)
+    dgs_raster_ctx *c = &ws->c;
+    c->h_total = ws->h_counts + ws->last;  // counts arrive in stream order: the last one is the latest
+    int nr = 0;
+    return wait_count(c, stream, nr);
+}
+
+int render_raster_frame(RenderWs *ws, const RenderRasterIn &in, int f, int known_count, hipStream_t stream) {
+    dgs_raster_ctx *c = &ws->c;
+    const int P = in.P, device = c->device;
+    c->P = P;
+    c->M = SH_ROW / 3;
+    c->H = in.H;
+    c->W = in.W;
+    c->gx = div_up(c->W, TILE_X);
+    c->gy = div_up(c->H, TILE_Y);
+    c->s.bg = in.bg;
+    const int T = c->gx * c->gy, HW = c->H * c->W;
+    const bool redo = known_count >= 0;
+    // geometry (no clamped bytes), as raster_forward lays it out
+    size_t off_xy = 0, off_co = align_up(off_xy + 8ull * P), off_cd = align_up(off_co + 16ull * P),
+           off_t = align_up(off_cd + 16ull * P), off_o = align_up(off_t + 4ull * P), off_rad = align_up(off_o + 4ull * P);
+    size_t off_dk = align_up(off_rad + 4ull * P), off_dk2 = align_up(off_dk + 4ull * P), off_gid = align_up(off_dk2 + 4ull * P),
+           off_ord = align_up(off_gid + 4ull * P), off_ts = align_up(off_ord + 4ull * P);
+    size_t scan_tmp = 0, dsort_tmp = 0;
+    if (P > 0) {
+        DGS_HIP_CHECK(scan_tmp_bytes(device, P, stream, scan_tmp));
+        DGS_HIP_CHECK(sort_tmp_bytes<uint32_t>(device, P, 32, stream, dsort_tmp));
+    }
+    const size_t off_st = align_up(off_ts + 4ull * P);
+    if (int rc = c->geom.ensure(off_st + std::max(scan_tmp, dsort_tmp) + 256)) return rc;
+    char *g = (char *)c->geom.p;
+    c->xy = (float2 *)(g + off_xy);
+    c->conic_o = (float4 *)(g + off_co);
+    c->rgbd = (float4 *)(g + off_cd);
+    c->tiles = (uint32_t *)(g + off_t);
+    c->offsets = (uint32_t *)(g + off_o);
+    c->radii = (int *)(g + off_rad);
+    c->dkey = (uint32_t *)(g + off_dk);
+    c->dkey_alt = (uint32_t *)(g + off_dk2);
+    c->gid = (uint32_t *)(g + off_gid);
+    c->order = (uint32_t *)(g + off_ord);
+    c->tiles_sorted = (uint32_t *)(g + off_ts);
+    c->clamped = nullptr;
+    if (int rc = c->img.ensure(8ull * T)) return rc;  // the tile ranges only
+    c->ranges = (uint2 *)c->img.p;
+    c->final_T = nullptr;
+    c->n_contrib = nullptr;
+    c->rect_mode = P > 0 && rect_binning(c->gx, c->gy, P);
+    if (c->rect_mode) {
+        const size_t nb = div_up(P, 256);
+        size_t o_st = align_up(4ull * nb * T), o_n = align_up(o_st + 4ull * T);
+        if (int rc = c->rect.ensure(o_n + 256)) return rc;
+        char *r = (char *)c->rect.p;
+        c->rect_cnt = (uint32_t *)r;
+        c->rect_start = (uint32_t *)(r + o_st);
+        c->rect_total = (uint32_t *)(r + o_n);
+        const size_t tot_cap = c->rtot.cap;
+        if (int rc = c->rtot.ensure(8ull * T)) return rc;
+        if (c->rtot.cap != tot_cap) DGS_HIP_CHECK(hipMemsetAsync(c->rtot.p, 0, c->rtot.cap, stream));
+        c->rect_tot = (unsigned long long *)c->rtot.p;
+    }
+    c->tsort = c->rect_mode && tile_sort_enabled();
+    c->det_fwd = false;
+    c->seg_ok = false;
+    if (redo && in.depth8) DGS_HIP_CHECK(hipMemsetAsync(ws->dmax + f, 0, 4, stream));
+    int cap = 0;
+    if (P > 0) {
+        const float fx = c->W / (2.f * in.tanfovx), fy = c->H / (2.f * in.tanfovy);
+        {
+            ScopedTimer tm("preprocess_img", stream);
+            hipLaunchKernelGGL((k_preprocess<true, true>), dim3(div_up(P, 256)), dim3(256), 0, stream, P, in.sh_degree,
+                               SH_ROW / 3, in.means3D, in.scales, in.scale_modifier, in.rotations, (const float *)nullptr,
+                               in.opacities, in.f_dc, in.f_rest, (const float *)nullptr, in.viewmatrix, in.projmatrix,
+                               in.campos, c->W, c->H, in.tanfovx, in.tanfovy, fx, fy, c->gx, c->gy, c->radii, c->xy,
+                               c->conic_o, c->rgbd, c->tiles, (uint8_t *)nullptr, c->dkey, c->gid, (float4 *)nullptr,
+                               (uint8_t *)nullptr);
+        }
+        DGS_LAUNCH_CHECK("k_preprocess", false, stream);
+        if (!c->tsort) {
+            ScopedTimer tm("depth_sort", stream);
+            if (hipcub_sort()) {
+                hipcub::DoubleBuffer<uint32_t> kb(c->dkey, c->dkey_alt), vb(c->gid, c->order);
+                DGS_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(g + off_st, dsort_tmp, kb, vb, P, 0, 32, stream));
+                c->order = vb.Current();
+                hipLaunchKernelGGL(k_gather_tiles, dim3(div_up(P, 256)), dim3(256), 0, stream, P, c->order, c->tiles,
+                                   c->tiles_sorted);
+            } else {
+                int alt = 0;
+                uint32_t *gid = c->gid, *ord = c->order;
+                if (int rc = radix::sort_pairs<uint32_t>(c->dkey, c->dkey_alt, gid, ord, P, 32, stream, &alt,
+                                                         c->rect_mode ? nullptr : c->tiles,
+                                                         c->rect_mode ? nullptr : c->tiles_sorted))
+                    return rc;
+                c->order = alt ? ord : gid;
+            }
+        }
+        DGS_LAUNCH_CHECK("depth_sort", false, stream);
+        // the frame's pair count: its own host word (a redo already knows it: the device-side dummy word)
+        c->h_total = ws->h_counts + f;
+        c->d_total = redo ? ws->dummy : ws->d_counts + f;
+        if (c->rect_mode) {
+            const int nb = div_up(P, 256);
+            {
+                ScopedTimer tm("count", stream);
+                hipLaunchKernelGGL(k_rect_count, dim3(nb), dim3(256), 4ull * T, stream, P, c->tsort ? nullptr : c->order,
+                                   c->xy, c->radii, c->gx, c->gy, c->rect_cnt, c->rect_total, (uint32_t *)nullptr);
+            }
+            DGS_LAUNCH_CHECK("k_rect_count", false, stream);
+            {
+                ScopedTimer tm("scan", stream);
+                hipLaunchKernelGGL(k_rect_colscan, dim3(div_up(T, 64)), dim3(1024), 0, stream, nb, T, c->rect_cnt, c->rect_tot,
+                                   next_rect_gen(), c->rect_total, c->rect_total + 1, c->rect_start, c->ranges, c->d_total);
+            }
+            DGS_LAUNCH_CHECK("k_rect_colscan", false, stream);
+        } else {
+            DGS_HIP_CHECK(hipcub::DeviceScan::InclusiveSum(g + off_st, scan_tmp, c->tiles_sorted, c->offsets, P, stream));
+            if (!redo) {
+                DGS_HIP_CHECK(hipMemcpyAsync(c->h_total, c->offsets + (P - 1), 4, hipMemcpyDeviceToHost, stream));
+                DGS_HIP_CHECK(hipEventRecord(c->count_ev, stream));  // wait_count waits on the latest record
+            }
+        }
+        if (!redo) ws->last = f;
+        cap = redo ? known_count : pair_cap_get(device);
+        if (!redo && cap <= 0) {  // no learned capacity: this frame waits for its own count, as the forward does
+            int nr = 0;
+            if (int rc = wait_count(c, stream, nr)) return rc;
+            cap = nr;
+            pair_cap_observe(device, nr);
+            ws->observed[(size_t)f] = 1;
+        }
+    }
+    ws->caps[(size_t)f] = cap;
+    if (int rc = bin_lists(c, cap, P, device, stream, false)) return rc;
+    const bool want8 = in.depth8 != nullptr;
+    float *depth = in.depth ? in.depth : (want8 ? ws->depth_scratch : nullptr);
+    const int pack_rgb = in.rgb8 && c->W % 4 == 0 && (reinterpret_cast<uintptr_t>(in.rgb8) & 3) == 0;
+    {
+        ScopedTimer tm("blend_img", stream);
+        hipLaunchKernelGGL(k_blend_img, dim3(T), dim3(TILE_PIX), 0, stream, c->ranges, c->vals, (uint32_t)cap, c->W, c->H,
+                           c->gx, c->xy, c->conic_o, c->rgbd, in.bg, in.color, depth, in.alpha, in.rgb8, pack_rgb,
+                           want8 ? ws->dmax + f : (uint32_t *)nullptr);
+    }
+    DGS_LAUNCH_CHECK("k_blend_img", false, stream);
+    if (want8) {
+        const int pack_d = HW % 4 == 0 && (reinterpret_cast<uintptr_t>(depth) & 15) == 0 &&
+                           (reinterpret_cast<uintptr_t>(in.depth8) & 3) == 0;
+        ScopedTimer tm("depth8", stream);
+        hipLaunchKernelGGL(k_depth8, dim3(div_up(div_up(HW, 4), 256)), dim3(256), 0, stream, HW, depth, ws->dmax + f,
+                           in.depth8, pack_d);
+        DGS_LAUNCH_CHECK("k_depth8", false, stream);
+    }
+    return DGS_OK;
+}
+}  // namespace dgs
 
 extern "C" int dgs_mark_visible(int P, const float *means3D, const float *viewmatrix, const float *projmatrix,
                                 uint8_t *visible, void *stream_) {

@@ -41,6 +41,24 @@ class RowJob(ctypes.Structure):
     _fields_ = [("src", P), ("dst", P), ("width", I)]
 
 
+class Frame(ctypes.Structure):
+    """dgs_frame (include/dgs.h)."""
+    _fields_ = [("viewmatrix", P), ("projmatrix", P), ("campos", P), ("tanfovx", F), ("tanfovy", F)]
+
+
+class RenderFramesArgs(ctypes.Structure):
+    """dgs_render_frames_args (include/dgs.h)."""
+    _fields_ = [
+        ("P", I), ("xyz", P), ("f_dc", P), ("f_rest", P), ("scaling", P), ("rotation", P), ("opacity", P),
+        ("deform", I), ("mlp_flags", I), ("mlp_packed", P), ("t", P), ("t_full", P),
+        ("mlp_out", P), ("means3D", P), ("scales", P), ("rotations", P), ("opacities", P),
+        ("H", I), ("W", I), ("sh_degree", I), ("scale_modifier", F), ("bg", P),
+        ("F", I), ("frames", ctypes.POINTER(Frame)),
+        ("out_color", P), ("out_depth", P), ("out_alpha", P), ("out_rgb8", P), ("out_depth8", P),
+        ("num_rendered", ctypes.POINTER(I)),
+    ]
+
+
 _SIGS = {
     "dgs_last_error": ([], ctypes.c_char_p),
     "dgs_version": ([], ctypes.c_char_p),
@@ -103,6 +121,8 @@ _SIGS = {
     "dgs_se3_backward": ([I, P, I, P, P, I, P], I),
     # (dgs_train_step_args*, int* overflowed, int* num_rendered, stream): deformgs/native_step.py
     "dgs_train_step": ([P, ctypes.POINTER(I), ctypes.POINTER(I), P], I),
+    # (dgs_render_frames_args*, int* redone_frames, stream): deformgs/render_frames.py
+    "dgs_render_frames": ([ctypes.POINTER(RenderFramesArgs), ctypes.POINTER(I), P], I),
 }
 
 EXPORTED = tuple(_SIGS)

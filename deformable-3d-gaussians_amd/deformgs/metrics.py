@@ -1,0 +1,103 @@
+"""python -m deformgs.metrics -m MODEL [MODEL ...] — the counterpart of metrics.py:39-98.
+
+For every <MODEL>/test/ours_* directory: per-view and mean PSNR (loss.psnr) and SSIM between renders/ and gt/
+(8-bit RGB PNGs read with deformgs/png.py, scaled to [0, 1] as torchvision's to_tensor does), written to
+<MODEL>/results.json ({method: {"SSIM", "PSNR", "LPIPS"}}) and <MODEL>/per_view.json ({method: {metric:
+{file name: value}}}) in the reference's layout. SSIM is the fused HIP loss kernel's mean SSIM
+(dgs_l1_ssim_forward: the reference's 11x11 sigma-1.5 window). LPIPS is recorded as null: the lpips package
+and its VGG weights are not assumed to be present.
+
+--synthetic N: when <MODEL>/test holds no ours_* directory yet, the test set of the synthetic scene is
+rendered first (deformgs.render_cli --mode render), so the script runs with no dataset.
+"""
+import argparse
+import json
+import os
+
+import torch
+
+from .loss import psnr
+from .png import read_png
+
+
+def fused_ssim(img, gt):
+    """Mean SSIM of two (1, 3, H, W) device images from the fused L1 + SSIM forward kernel."""
+    from . import _lib
+    lib = _lib.load()
+    a, b = img[0].float().contiguous(), gt[0].float().contiguous()
+    _lib.require_cuda(a, b)
+    C, H, W = a.shape
+    scratch = torch.empty(lib.dgs_l1_ssim_scratch_floats(C, H, W), dtype=torch.float32, device=a.device)
+    out = torch.empty(3, dtype=torch.float32, device=a.device)
+    _lib.check(lib.dgs_l1_ssim_forward(C, H, W, _lib.ptr(a), _lib.ptr(b), 0.2, _lib.ptr(out), _lib.ptr(scratch),
+                                       _lib.stream_ptr(a.device)), "l1_ssim_forward")
+    return out[2]
+
+
+def read_images(renders_dir, gt_dir, device):
+    """-> (renders, gts, names): (1, 3, H, W) float tensors in [0, 1] (metrics.py:25-36)."""
+    renders, gts, names = [], [], []
+    for fname in sorted(os.listdir(renders_dir)):
+        if not fname.endswith(".png"):
+            continue
+        pair = []
+        for d in (renders_dir, gt_dir):
+            a = read_png(os.path.join(d, fname))
+            if a.ndim != 3:
+                raise ValueError(f"{os.path.join(d, fname)}: expected an 8-bit RGB PNG")
+            pair.append((torch.from_numpy(a).to(device).permute(2, 0, 1).contiguous().float() / 255.0).unsqueeze(0))
+        renders.append(pair[0])
+        gts.append(pair[1])
+        names.append(fname)
+    return renders, gts, names
+
+
+def evaluate(model_paths, ssim_fn=None, device="cuda"):
+    """Writes results.json / per_view.json under every model path; -> {model path: results dict}."""
+    ssim_fn = ssim_fn or fused_ssim
+    full = {}
+    for scene_dir in model_paths:
+        print("Scene:", scene_dir)
+        full[scene_dir], per_view = {}, {}
+        test_dir = os.path.join(scene_dir, "test")
+        for method in sorted(os.listdir(test_dir)):
+            if not method.startswith("ours"):
+                continue
+            print("Method:", method)
+            renders, gts, names = read_images(os.path.join(test_dir, method, "renders"),
+                                              os.path.join(test_dir, method, "gt"), device)
+            ssims = [float(ssim_fn(r, g)) for r, g in zip(renders, gts)]
+            psnrs = [float(psnr(r, g)) for r, g in zip(renders, gts)]
+            m_ssim, m_psnr = torch.tensor(ssims).mean().item(), torch.tensor(psnrs).mean().item()
+            print("  SSIM : {:>12.7f}".format(m_ssim))
+            print("  PSNR : {:>12.7f}".format(m_psnr))
+            print("  LPIPS: not computed\n")
+            full[scene_dir][method] = {"SSIM": m_ssim, "PSNR": m_psnr, "LPIPS": None}
+            per_view[method] = {"SSIM": dict(zip(names, torch.tensor(ssims).tolist())),
+                                "PSNR": dict(zip(names, torch.tensor(psnrs).tolist())),
+                                "LPIPS": {n: None for n in names}}
+        with open(os.path.join(scene_dir, "results.json"), "w") as fp:
+            json.dump(full[scene_dir], fp, indent=True)
+        with open(os.path.join(scene_dir, "per_view.json"), "w") as fp:
+            json.dump(per_view, fp, indent=True)
+    return full
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="PSNR / SSIM of rendered test sets (metrics.py counterpart)")
+    ap.add_argument("--model_paths", "-m", required=True, nargs="+")
+    ap.add_argument("--synthetic", type=int, default=0, metavar="N")
+    ap.add_argument("--res", type=int, nargs=2, default=[800, 800], metavar=("W", "H"))
+    args = ap.parse_args(argv)
+    if args.synthetic:
+        from . import render_cli
+        for m in args.model_paths:
+            t = os.path.join(m, "test")
+            if not (os.path.isdir(t) and any(d.startswith("ours") for d in os.listdir(t))):
+                render_cli.main(["-m", m, "--synthetic", str(args.synthetic), "--res", str(args.res[0]), str(args.res[1]),
+                                 "--mode", "render", "--skip_train"])
+    return evaluate(args.model_paths)
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,175 @@
+"""python -m deformgs.render_cli -m MODEL --mode {render,time,view,all,pose,original} — the counterpart of
+render_baseline.py:299-350 on render_frames.
+
+Loads MODEL/point_cloud/iteration_k/point_cloud.ply and MODEL/deform/iteration_k/deform.pth, builds the
+mode's frame list (deformgs/camera_paths.py), renders it with render_frames (8-bit colour and depth straight
+from the blend kernel) and writes <MODEL>/<train|test>/<mode dir>_<k>/renders/%05d.png, depth/%05d.png and,
+for mode render, gt/%05d.png — the reference's directory names — with the stdlib PNG writer. Prints the
+reference's FPS line for every set (frames / elapsed of the render_frames call between two device
+synchronisations). No video is written (MP4 encoding is out of scope).
+
+Cameras: --synthetic N takes the synthetic scene of deformgs/train.py (N Gaussians, --res W H); when MODEL
+holds no saved model yet, the scene's own initial Gaussians and a fresh network (heads at 1/100 scale) are
+saved there as iteration 0 first, so the script runs with no dataset. -s SOURCE reads a D-NeRF style
+transforms_train.json / transforms_test.json (camera_angle_x, per frame transform_matrix and time;
+dataset_readers.py:222-262) for the cameras; ground-truth images are written only for views that carry one.
+"""
+import argparse
+import json
+import math
+import os
+import time
+
+import numpy as np
+import torch
+
+from .camera_paths import DIR_NAMES, MODES, frame_list
+from .cameras import Camera, blender_c2w_to_RT, focal2fov, fov2focal
+from .png import write_png
+
+
+class _Set:
+    def __init__(self, train, test):
+        self.train, self.test = train, test
+
+
+def read_transforms(source, width, height, device):
+    """D-NeRF transforms_{train,test}.json -> _Set of Cameras without images (dataset_readers.py:222-262)."""
+    sets = {}
+    for name in ("train", "test"):
+        path = os.path.join(source, f"transforms_{name}.json")
+        cams = []
+        if os.path.exists(path):
+            with open(path) as f:
+                meta = json.load(f)
+            fovx = float(meta["camera_angle_x"])
+            frames = meta["frames"]
+            for k, fr in enumerate(frames):
+                R, T = blender_c2w_to_RT(np.array(fr["transform_matrix"]))
+                fovy = focal2fov(fov2focal(fovx, width), height)
+                fid = float(fr["time"]) if "time" in fr else k / max(len(frames) - 1, 1)
+                # dataset_readers.py:260-262 swaps the names: FovY = fovx, FovX = fovy
+                cams.append(Camera(R, T, FoVx=fovy, FoVy=fovx, width=width, height=height, fid=fid, uid=k,
+                                   data_device=device))
+        sets[name] = cams
+    return _Set(sets["train"], sets["test"])
+
+
+def _iteration(model_path, iteration):
+    from .deform_model import searchForMaxIteration
+    if iteration >= 0:
+        return iteration
+    return searchForMaxIteration(os.path.join(model_path, "point_cloud"))
+
+
+def load_scene(args, device="cuda"):
+    """-> (gaussians, deform, camera sets, background, iteration) for the parsed arguments."""
+    from .deform_model import DeformModelBaseline
+    from .gaussian_model import GaussianModel
+    dev = torch.device(device)
+    W, H = args.res
+    if args.synthetic:
+        from .train import SyntheticScene
+        scene = SyntheticScene(args.synthetic, W, H, device=dev, white_background=args.white_background)
+        cams = _Set(scene.getTrainCameras(), scene.getTestCameras())
+        if not os.path.isdir(os.path.join(args.model_path, "point_cloud")):
+            g0 = scene.init_gaussians(GaussianModel(3))
+            g0.save_ply(os.path.join(args.model_path, "point_cloud", "iteration_0", "point_cloud.ply"))
+            torch.manual_seed(0)
+            d0 = DeformModelBaseline(not args.non_blender, args.is_6dof, device=dev)
+            net = d0.deform
+            heads = (net.branch_w, net.branch_v) if args.is_6dof else (net.gaussian_warp,)
+            with torch.no_grad():
+                for head in heads + (net.gaussian_rotation, net.gaussian_scaling):
+                    head.weight.mul_(0.01)
+                    head.bias.mul_(0.01)
+            d0.save_weights(args.model_path, 0)
+    elif args.source_path:
+        cams = read_transforms(args.source_path, W, H, dev)
+    else:
+        raise SystemExit("render_cli: give the cameras with --synthetic N or -s SOURCE (transforms_*.json)")
+    it = _iteration(args.model_path, args.iteration)
+    gaussians = GaussianModel(args.sh_degree)
+    gaussians.load_ply(os.path.join(args.model_path, "point_cloud", f"iteration_{it}", "point_cloud.ply"), device=dev)
+    deform = DeformModelBaseline(not args.non_blender, args.is_6dof, device=dev)
+    deform.load_weights(args.model_path, iteration=it)
+    bg = torch.tensor([1.0, 1.0, 1.0] if args.white_background else [0.0, 0.0, 0.0], device=dev)
+    return gaussians, deform, cams, bg, it
+
+
+def frame_cameras(mode, views, view_index=0, frames=None):
+    """The mode's frames as (Cameras, times): mode render keeps the views themselves."""
+    if mode == "render":
+        return list(views), [float(v.fid) for v in views]
+    v0 = views[view_index]
+    fl = frame_list(mode, views, view_index, frames)
+    cams = [Camera(R, T, v0.FoVx, v0.FoVy, v0.image_width, v0.image_height, fid=t, trans=v0.trans, scale=v0.scale,
+                   data_device=v0.data_device) for R, T, t in fl]
+    return cams, [t for _, _, t in fl]
+
+
+def render_set(model_path, name, iteration, mode, views, gaussians, deform, background, is_6dof, view_index=0,
+               frames=None, chunk=None):
+    """Renders one camera set for `mode`, writes the PNGs, prints the FPS line. -> the output directory."""
+    from .render_frames import render_frames
+    base = os.path.join(model_path, name, f"{DIR_NAMES[mode]}_{iteration}")
+    dirs = {k: os.path.join(base, k) for k in (("renders", "depth", "gt") if mode == "render" else ("renders", "depth"))}
+    for d in dirs.values():
+        os.makedirs(d, exist_ok=True)
+    cams, times = frame_cameras(mode, views, view_index, frames)
+    torch.cuda.synchronize()
+    t0 = time.time()
+    out = render_frames(cams, gaussians, deform, background, times=times, is_6dof=is_6dof, outputs=("rgb8", "depth8"),
+                        chunk=chunk)
+    torch.cuda.synchronize()
+    dt = time.time() - t0
+    rgb, dep = out["rgb8"].cpu().numpy(), out["depth8"].cpu().numpy()
+    for i in range(len(cams)):
+        write_png(os.path.join(dirs["renders"], f"{i:05d}.png"), rgb[i])
+        write_png(os.path.join(dirs["depth"], f"{i:05d}.png"), dep[i])
+        if mode == "render" and getattr(cams[i], "original_image", None) is not None:
+            gt = cams[i].original_image[0:3]
+            gt8 = (255 * gt.clamp(0, 1)).to(torch.uint8).permute(1, 2, 0).contiguous().cpu().numpy()
+            write_png(os.path.join(dirs["gt"], f"{i:05d}.png"), gt8)
+    fps = len(cams) / dt if dt > 0 and cams else 0.0
+    print(f"Test FPS: \033[1;35m{fps:.5f}\033[0m, Num. of GS: {gaussians.get_xyz.shape[0]}", flush=True)
+    return base
+
+
+def build_parser():
+    ap = argparse.ArgumentParser(description="Render a trained deformable-Gaussian model (render_baseline.py counterpart)")
+    ap.add_argument("--model_path", "-m", required=True)
+    ap.add_argument("--source_path", "-s", default="")
+    ap.add_argument("--mode", default="render", choices=list(MODES))
+    ap.add_argument("--iteration", default=-1, type=int)
+    ap.add_argument("--skip_train", action="store_true")
+    ap.add_argument("--skip_test", action="store_true")
+    ap.add_argument("--synthetic", type=int, default=0, metavar="N")
+    ap.add_argument("--res", type=int, nargs=2, default=[800, 800], metavar=("W", "H"))
+    ap.add_argument("--frames", type=int, default=None, help="frames of an interpolation mode (default: the reference's)")
+    ap.add_argument("--view_index", type=int, default=-1, help="the fixed view of time / view / all / pose (-1: random)")
+    ap.add_argument("--sh_degree", type=int, default=3)
+    ap.add_argument("--white_background", action="store_true")
+    ap.add_argument("--is_6dof", action="store_true")
+    ap.add_argument("--non_blender", action="store_true")
+    ap.add_argument("--chunk", type=int, default=None)
+    return ap
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    print("Rendering " + args.model_path)
+    with torch.no_grad():
+        gaussians, deform, cams, bg, it = load_scene(args)
+        done = []
+        for name, views, skip in (("train", cams.train, args.skip_train), ("test", cams.test, args.skip_test)):
+            if skip or not views:
+                continue
+            idx = args.view_index if args.view_index >= 0 else int(torch.randint(0, len(views), (1,)).item())
+            done.append(render_set(args.model_path, name, it, args.mode, views, gaussians, deform, bg, args.is_6dof,
+                                   view_index=idx, frames=args.frames, chunk=args.chunk))
+    return done
+
+
+if __name__ == "__main__":
+    main()

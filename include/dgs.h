@@ -22,6 +22,8 @@
  *                           exp(scaling) + d_scaling, normalize(rotation) + d_rotation, sigmoid(opacity),
  *                           cat(features_dc, features_rest)) and its autograd; *_se3_* and dgs_se3_*
  *                           the 6-DoF branch (gaussian_renderer/__init__.py:71-76, utils/rigid_utils.py)
+ *   dgs_render_frames    <- the frame loops of render_baseline.py (render_set :57-66 and the interpolate_*
+ *                           variants): deform.step + render() per (camera, time) pair, forward only
  *   dgs_adam_step        <- torch.optim.Adam(..., eps=1e-15).step() of scene/gaussian_model.py:132 and
  *                           scene/deform_model.py:266 (train_baseline.py:176-182)
  */
@@ -370,6 +372,54 @@ typedef struct dgs_train_step_args {
     int phase;                           /* 0 (= 3), 1, 2, 3: see above */
 } dgs_train_step_args;
 int dgs_train_step(const dgs_train_step_args *a, int *overflowed, int *num_rendered, void *stream);
+
+/* ---- F frames of one model in one call, forward only (render_baseline.py:57-66 per frame) ----
+ * Frame f = deform.step(xyz, t[f]) -> render() input glue -> rasterizer forward, enqueued back to back on
+ * one stream. No backward state exists: no dgs_raster_ctx is handed out or taken from the context pool, and
+ * there are no gradient accumulators, no final_T / n_contrib / clamped / checkpoints; the workspace (which
+ * uses that struct internally as the container of its geometry / binning buffer views) is cached per
+ * device and grows as DevBuf does. The network runs
+ * with the flags DeformNetwork.raw passes under no_grad (DGS_MLP_UNIFORM_T, no saved activations), so
+ * colour and depth are bitwise those of the per-frame path (dgs_deform_forward + dgs_gaussian_inputs_* +
+ * dgs_raster_forward_split_sh).
+ * Pair counts: every frame is binned for the learned per-device pair capacity and writes its count into its
+ * own word of a mapped host array; the call waits once, at its end, and re-renders (from the deformation
+ * on, at the exact size) every frame whose count exceeded the capacity it was binned with; *redone_frames
+ * (may be NULL) counts them. Without a learned capacity the first frame waits for its own count, as
+ * dgs_raster_forward does. num_rendered[f] (host, may be NULL) is frame f's exact pair count; the
+ * outputs are complete in stream order.
+ * mlp_packed: the network's weights as dgs_deform_pack(mlp_flags | DGS_MLP_UNIFORM_T) wrote them (read
+ * only). t_full may be NULL exactly where dgs_train_step allows it. deform = 0: static Gaussians
+ * (deltas 0.0), no network buffers needed. F = 0 and P = 0 are valid (P = 0: every frame is the
+ * background, out_alpha 0). At least one output must be non-NULL; f_dc / f_rest 16-byte aligned;
+ * sh_degree <= 3. */
+typedef struct dgs_frame {          /* host array of F */
+    const float *viewmatrix, *projmatrix, *campos;   /* device, as dgs_raster_settings */
+    float tanfovx, tanfovy;
+} dgs_frame;
+
+typedef struct dgs_render_frames_args {
+    int P;
+    const float *xyz, *f_dc, *f_rest, *scaling, *rotation, *opacity;   /* as dgs_train_step_args */
+    int deform;                      /* 0: static Gaussians (deltas 0.0) */
+    int mlp_flags;
+    const float *mlp_packed;
+    const float *t;                  /* device (F,): frame times */
+    float *t_full;                   /* P floats scratch */
+    float *mlp_out, *means3D, *scales, *rotations, *opacities;   /* per-frame scratch, reused */
+    int H, W, sh_degree;
+    float scale_modifier;
+    const float *bg;                 /* (3,) device */
+    int F;
+    const dgs_frame *frames;
+    float *out_color;                /* (F,3,H,W) or NULL */
+    float *out_depth;                /* (F,1,H,W) or NULL */
+    float *out_alpha;                /* (F,1,H,W) = 1 - final transmittance, or NULL */
+    uint8_t *out_rgb8;               /* (F,H,W,3) = trunc(255 * clamp(c, 0, 1)) (the reference's to8b), or NULL */
+    uint8_t *out_depth8;             /* (F,H,W) = trunc(255 * clamp(depth / (max_frame(depth) + 1e-5), 0, 1)), or NULL */
+    int *num_rendered;               /* host (F,) */
+} dgs_render_frames_args;
+int dgs_render_frames(const dgs_render_frames_args *a, int *redone_frames, void *stream);
 
 #ifdef __cplusplus
 }
