@@ -123,6 +123,10 @@ _SIGS = {
     "dgs_train_step": ([P, ctypes.POINTER(I), ctypes.POINTER(I), P], I),
     # (dgs_render_frames_args*, int* redone_frames, stream): deformgs/render_frames.py
     "dgs_render_frames": ([ctypes.POINTER(RenderFramesArgs), ctypes.POINTER(I), P], I),
+    # dataset image ingest: deformgs/ingest.py
+    "dgs_ingest_unfilter": ([I, I, I, I, P, P, P, P], I),
+    "dgs_ingest_resample": ([ctypes.c_int64, I, I, I, P, P, P, I, P, P], I),
+    "dgs_ingest_to_float": ([I, I, I, P, P, P], I),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -1,0 +1,261 @@
+"""D-NeRF (Blender-style) dataset directories: the counterpart of scene.Scene / readNerfSyntheticInfo.
+
+Mirrors (file:line in the reference):
+  scene/dataset_readers.py:223-266  readCamerasFromTransforms: R / T from transform_matrix, fid = frame["time"],
+                                    FovY = camera_angle_x and FovX from it (the names are swapped there, and
+                                    the swap is kept, as deformgs/render_cli.read_transforms does)
+  scene/dataset_readers.py:269-306  readNerfSyntheticInfo: test merged into train unless eval; getNerfppNorm;
+                                    points3d.ply or 100 000 random points in [-1.3, 1.3]^3
+  scene/dataset_readers.py:77-98    getNerfppNorm: translate = -mean camera centre, radius = 1.1 x largest
+                                    distance from it
+  utils/camera_utils.py:21-44       loadCam's resolution rule (target_resolution)
+  utils/camera_utils.py:69-89       camera_to_JSON
+  scene/__init__.py:23-112          Scene: input.ply, cameras.json, the camera lists, create_from_pcd
+
+The images go through deformgs/ingest.py (HIP unfilter + composite + resize on a GPU device), one batch per
+camera set; every camera's original_image is a view into that batch.
+
+Deviation: the reference writes the random point cloud into the dataset directory (points3d.ply). Here SOURCE
+is read only; the cloud is written as MODEL/input.ply, where the reference copies it anyway, and a later run
+draws the same cloud again from its seed.
+
+Out of scope (they need cv2 / imageio behaviour): the NeRF-DS / Nerfies / HyperNeRF, Colmap, DTU and
+plenoptic readers; gt_alpha_mask and load2gpu_on_the_fly.
+"""
+import json
+import os
+from argparse import Namespace
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from .cameras import Camera, blender_c2w_to_RT, focal2fov, fov2focal, getWorld2View2
+from .sh import C0
+
+CameraInfo = namedtuple("CameraInfo", "uid R T FovY FovX image_path image_name width height fid")
+SceneInfo = namedtuple("SceneInfo", "point_cloud train_cameras test_cameras nerf_normalization ply_path")
+BasicPointCloud = namedtuple("BasicPointCloud", "points colors normals")
+
+_PLY_TYPES = {"float": "<f4", "float32": "<f4", "double": "<f8", "float64": "<f8", "uchar": "u1", "uint8": "u1",
+              "char": "i1", "int8": "i1", "short": "<i2", "int16": "<i2", "ushort": "<u2", "uint16": "<u2",
+              "int": "<i4", "int32": "<i4", "uint": "<u4", "uint32": "<u4"}
+
+
+def png_size(path):
+    """(width, height) from the IHDR of a PNG file (no decode)."""
+    with open(path, "rb") as f:
+        head = f.read(24)
+    if len(head) < 24 or head[:8] != b"\x89PNG\r\n\x1a\n" or head[12:16] != b"IHDR":
+        raise ValueError(f"{path}: not a PNG file")
+    return int.from_bytes(head[16:20], "big"), int.from_bytes(head[20:24], "big")
+
+
+def read_cameras_from_transforms(path, transformsfile, extension=".png"):
+    """dataset_readers.py:223-266 without the image load (the images are ingested per set, in one batch)."""
+    with open(os.path.join(path, transformsfile)) as f:
+        contents = json.load(f)
+    fovx = contents["camera_angle_x"]
+    infos = []
+    for idx, frame in enumerate(contents["frames"]):
+        image_path = os.path.join(path, frame["file_path"] + extension)
+        R, T = blender_c2w_to_RT(np.array(frame["transform_matrix"]))
+        width, height = png_size(image_path)
+        fovy = focal2fov(fov2focal(fovx, width), height)
+        # :257-259 swaps the names: FovY = fovx, FovX = fovy
+        infos.append(CameraInfo(uid=idx, R=R, T=T, FovY=fovx, FovX=fovy, image_path=image_path,
+                                image_name=os.path.splitext(os.path.basename(image_path))[0], width=width,
+                                height=height, fid=frame["time"]))
+    return infos
+
+
+def nerfpp_norm(cam_infos):
+    """dataset_readers.py:77-98 getNerfppNorm."""
+    centers = np.hstack([np.linalg.inv(getWorld2View2(c.R, c.T))[:3, 3:4] for c in cam_infos])
+    center = np.mean(centers, axis=1, keepdims=True)
+    diagonal = np.max(np.linalg.norm(centers - center, axis=0, keepdims=True))
+    return {"translate": -center.flatten(), "radius": diagonal * 1.1}
+
+
+def store_ply(path, xyz, rgb):
+    """dataset_readers.py:154-169 storePly: x y z nx ny nz float, red green blue uchar, binary little endian."""
+    n = xyz.shape[0]
+    el = np.zeros(n, dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"),
+                            ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+    el["x"], el["y"], el["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    rgb8 = np.asarray(rgb).astype(np.uint8)  # truncation, as the structured assignment upstream
+    el["red"], el["green"], el["blue"] = rgb8[:, 0], rgb8[:, 1], rgb8[:, 2]
+    header = f"ply\nformat binary_little_endian 1.0\nelement vertex {n}\n"
+    header += "".join(f"property {'uchar' if el.dtype[name].itemsize == 1 else 'float'} {name}\n" for name in el.dtype.names)
+    with open(path, "wb") as f:
+        f.write((header + "end_header\n").encode("ascii"))
+        f.write(el.tobytes())
+
+
+def fetch_ply(path):
+    """dataset_readers.py:144-151 fetchPly for a binary little-endian vertex element of scalar properties."""
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError(f"{path}: not a PLY file")
+        fields, n, in_vertex = [], None, False
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError(f"{path}: PLY header without end_header")
+            parts = line.decode("ascii").split()
+            if not parts:
+                continue
+            if parts[0] == "format" and parts[1] != "binary_little_endian":
+                raise ValueError(f"{path}: only binary_little_endian PLY is supported")
+            if parts[0] == "element":
+                in_vertex = parts[1] == "vertex"
+                if in_vertex:
+                    n = int(parts[2])
+            elif parts[0] == "property" and in_vertex:
+                if parts[1] not in _PLY_TYPES:
+                    raise ValueError(f"{path}: PLY property type {parts[1]}")
+                fields.append((parts[-1], _PLY_TYPES[parts[1]]))
+            elif parts[0] == "end_header":
+                break
+        if n is None:
+            raise ValueError(f"{path}: PLY without a vertex element")
+        dt = np.dtype(fields)
+        buf = f.read(n * dt.itemsize)
+    if len(buf) != n * dt.itemsize:
+        raise ValueError(f"{path}: PLY vertex data is short")
+    v = np.frombuffer(buf, dtype=dt, count=n)
+    # row-major copies: create_from_pcd turns them into the (contiguous) Gaussian parameters as they are
+    points = np.ascontiguousarray(np.vstack([v["x"], v["y"], v["z"]]).T)
+    colors = np.ascontiguousarray(np.vstack([v["red"], v["green"], v["blue"]]).T) / 255.0
+    names = set(dt.names)
+    normals = (np.ascontiguousarray(np.vstack([v["nx"], v["ny"], v["nz"]]).T) if {"nx", "ny", "nz"} <= names
+               else np.zeros_like(points))
+    return BasicPointCloud(points=points, colors=colors, normals=normals)
+
+
+def random_point_cloud(num_pts, seed=0):
+    """dataset_readers.py:286-293: positions uniform in [-1.3, 1.3]^3, colours SH2RGB(U[0, 1) / 255), from a
+    seeded generator (the reference draws from numpy's global state). -> (xyz, rgb in [0, 1])."""
+    rng = np.random.default_rng(seed)
+    xyz = rng.random((num_pts, 3)) * 2.6 - 1.3
+    shs = rng.random((num_pts, 3)) / 255.0
+    return xyz, shs * C0 + 0.5
+
+
+def read_nerf_synthetic(path, white_background, eval, extension=".png", init_points=100_000, model_path=None, seed=0):
+    """dataset_readers.py:269-306. white_background is applied when the images are ingested (Scene); it is
+    kept in the signature of the reference. The point cloud is SOURCE/points3d.ply if present; otherwise
+    `init_points` seeded random points, written to MODEL/input.ply when model_path is given (never under
+    SOURCE) and read back from there, so the colours carry the file's 8-bit rounding as upstream."""
+    train = read_cameras_from_transforms(path, "transforms_train.json", extension)
+    test = read_cameras_from_transforms(path, "transforms_test.json", extension)
+    if not eval:
+        train.extend(test)
+        test = []
+    norm = nerfpp_norm(train)
+    ply_path = os.path.join(path, "points3d.ply")
+    if os.path.exists(ply_path):
+        pcd = fetch_ply(ply_path)
+    else:
+        xyz, rgb = random_point_cloud(init_points, seed)
+        ply_path = None
+        if model_path:
+            os.makedirs(model_path, exist_ok=True)
+            ply_path = os.path.join(model_path, "input.ply")
+            store_ply(ply_path, xyz, rgb * 255)
+            pcd = fetch_ply(ply_path)
+        else:
+            pcd = BasicPointCloud(points=xyz.astype(np.float32), colors=(rgb * 255).astype(np.uint8) / 255.0,
+                                  normals=np.zeros((init_points, 3)))
+    return SceneInfo(point_cloud=pcd, train_cameras=train, test_cameras=test, nerf_normalization=norm, ply_path=ply_path)
+
+
+def target_resolution(orig_w, orig_h, resolution):
+    """camera_utils.py:24-42 at resolution_scale 1: -r in {1, 2, 4, 8} -> round(orig / r) per axis (Python's
+    round: halves go to even); -1 -> full size unless wider than 1600; anything else is a target width."""
+    if resolution in (1, 2, 4, 8):
+        return round(orig_w / resolution), round(orig_h / resolution)
+    if resolution == -1:
+        global_down = orig_w / 1600 if orig_w > 1600 else 1
+    else:
+        global_down = orig_w / resolution
+    scale = float(global_down)
+    return int(orig_w / scale), int(orig_h / scale)
+
+
+def camera_to_json(id, cam):
+    """camera_utils.py:69-89 on a CameraInfo."""
+    Rt = np.zeros((4, 4))
+    Rt[:3, :3] = cam.R.transpose()
+    Rt[:3, 3] = cam.T
+    Rt[3, 3] = 1.0
+    W2C = np.linalg.inv(Rt)
+    return {"id": id, "img_name": cam.image_name, "width": cam.width, "height": cam.height,
+            "position": W2C[:3, 3].tolist(), "rotation": [x.tolist() for x in W2C[:3, :3]],
+            "fy": fov2focal(cam.FovY, cam.height), "fx": fov2focal(cam.FovX, cam.width)}
+
+
+def load_cameras(cam_infos, resolution, white_background, device):
+    """camera_utils.py:60-66 cameraList_from_camInfos: one ingest batch for the set, one Camera per view."""
+    from .ingest import ingest_images
+    if not cam_infos:
+        return []
+    images = ingest_images([c.image_path for c in cam_infos], white_background,
+                           size=lambda w, h: target_resolution(w, h, resolution), device=device)
+    cams = []
+    for i, c in enumerate(cam_infos):
+        cam = Camera(c.R, c.T, FoVx=c.FovX, FoVy=c.FovY, width=images.shape[3], height=images.shape[2], fid=c.fid,
+                     uid=i, data_device=device)
+        cam.original_image = images[i]
+        cam.image_name = c.image_name
+        cams.append(cam)
+    return cams
+
+
+class Scene:
+    """scene/__init__.py:23-112 for a D-NeRF directory. args: source_path, model_path, white_background, eval,
+    resolution (default -1), init_points (default 100 000), data_device (default "cuda")."""
+
+    def __init__(self, args, gaussians, load_iteration=None):
+        from .deform_model import searchForMaxIteration
+        self.model_path = args.model_path
+        self.gaussians = gaussians
+        self.loaded_iter = None
+        if load_iteration is not None:
+            self.loaded_iter = (searchForMaxIteration(os.path.join(self.model_path, "point_cloud"))
+                                if load_iteration == -1 else load_iteration)
+        if not os.path.exists(os.path.join(args.source_path, "transforms_train.json")):
+            raise ValueError(f"{args.source_path}: no transforms_train.json (only D-NeRF style datasets are read)")
+        device = torch.device(getattr(args, "data_device", "cuda"))
+        os.makedirs(self.model_path, exist_ok=True)
+        info = read_nerf_synthetic(args.source_path, args.white_background, args.eval,
+                                   init_points=getattr(args, "init_points", 100_000),
+                                   model_path=None if self.loaded_iter else self.model_path)
+        if not self.loaded_iter:
+            dest = os.path.join(self.model_path, "input.ply")
+            if info.ply_path != dest:  # SOURCE/points3d.ply: copied, as upstream
+                with open(info.ply_path, "rb") as src, open(dest, "wb") as dst:
+                    dst.write(src.read())
+            camlist = list(info.test_cameras) + list(info.train_cameras)
+            with open(os.path.join(self.model_path, "cameras.json"), "w") as f:
+                json.dump([camera_to_json(i, c) for i, c in enumerate(camlist)], f)
+            with open(os.path.join(self.model_path, "cfg_args"), "w") as f:
+                f.write(str(Namespace(**{k: v for k, v in sorted(vars(args).items())})))
+        self.cameras_extent = float(info.nerf_normalization["radius"])
+        resolution = getattr(args, "resolution", -1)
+        self.train_cameras = load_cameras(info.train_cameras, resolution, args.white_background, device)
+        self.test_cameras = load_cameras(info.test_cameras, resolution, args.white_background, device)
+        if self.loaded_iter:
+            self.gaussians.load_ply(os.path.join(self.model_path, "point_cloud", f"iteration_{self.loaded_iter}",
+                                                 "point_cloud.ply"), device=device)
+        else:
+            self.gaussians.create_from_pcd(info.point_cloud, self.cameras_extent, device=device)
+
+    def save(self, iteration):
+        self.gaussians.save_ply(os.path.join(self.model_path, "point_cloud", f"iteration_{iteration}", "point_cloud.ply"))
+
+    def getTrainCameras(self):
+        return self.train_cameras
+
+    def getTestCameras(self):
+        return self.test_cameras

@@ -1,7 +1,8 @@
-"""A PNG writer and reader on the standard library alone (zlib + struct): 8-bit RGB and 8-bit grey,
-non-interlaced. The render script writes renders/ depth/ gt/ with it and the metrics script reads them
-back (the reference uses torchvision.utils.save_image and PIL, render_baseline.py:44-55 / metrics.py:25-37;
-neither is assumed here)."""
+"""A PNG writer and reader on the standard library alone (zlib + struct), 8 bits per channel, non-interlaced:
+the writer RGB and grey, the reader also RGBA and grey + alpha (the D-NeRF images are RGBA). The render
+script writes renders/ depth/ gt/ with it and the metrics script reads them back (the reference uses
+torchvision.utils.save_image and PIL, render_baseline.py:44-55 / metrics.py:25-37; neither is assumed here).
+inflate_png stops before the unfiltering: deformgs/ingest.py does that on the device."""
 import struct
 import zlib
 
@@ -31,14 +32,13 @@ def write_png(path, img, level=6):
         f.write(encode_png(img, level))
 
 
-def _paeth(a, b, c):
-    p = a + b - c
-    pa, pb, pc = abs(p - a), abs(p - b), abs(p - c)
-    return a if (pa <= pb and pa <= pc) else (b if pb <= pc else c)
+_CHANNELS = {0: 1, 2: 3, 4: 2, 6: 4}  # colour type -> channels at 8 bits
 
 
-def decode_png(data):
-    """-> uint8 array (H, W, 3) or (H, W). 8-bit RGB / grey, the five filter types, no interlace."""
+def inflate_png(data):
+    """-> (W, H, channels, filtered_scanlines): the chunk parse, header check and zlib inflate of decode_png
+    without the unfiltering (H rows of one filter byte + W * channels bytes), for the device path of
+    deformgs/ingest.py. Raises ValueError on anything decode_png does not read."""
     if data[:8] != _SIG:
         raise ValueError("not a PNG file")
     pos, idat, hdr = 8, [], None
@@ -55,43 +55,63 @@ def decode_png(data):
     if hdr is None:
         raise ValueError("PNG without IHDR")
     w, h, depth, ctype, _, _, interlace = hdr
-    if depth != 8 or ctype not in (0, 2) or interlace != 0:
+    if depth != 8 or ctype not in _CHANNELS or interlace != 0:
         raise ValueError(f"unsupported PNG (bit depth {depth}, colour type {ctype}, interlace {interlace}): "
-                         "8-bit RGB or grey, non-interlaced only")
-    bpp = 3 if ctype == 2 else 1
-    stride = w * bpp
-    raw = zlib.decompress(b"".join(idat))
-    if len(raw) != h * (stride + 1):
+                         "8-bit RGB, RGBA, grey or grey + alpha, non-interlaced only")
+    bpp = _CHANNELS[ctype]
+    try:
+        raw = zlib.decompress(b"".join(idat))
+    except zlib.error as e:
+        raise ValueError(f"PNG data does not inflate: {e}") from None
+    if len(raw) != h * (w * bpp + 1):
         raise ValueError("PNG data length does not match its header")
-    out = np.zeros((h, stride), np.uint8)
-    prev = np.zeros(stride, np.int32)
-    for y in range(h):
-        ft = raw[y * (stride + 1)]
-        line = np.frombuffer(raw, np.uint8, stride, y * (stride + 1) + 1).astype(np.int32)
-        if ft == 0:
-            cur = line
-        elif ft == 2:
-            cur = (line + prev) & 255
-        elif ft == 1:  # Sub: a running sum per channel
-            cur = (np.cumsum(line.reshape(w, bpp), axis=0) & 255).reshape(-1)
-        elif ft in (3, 4):  # Average / Paeth depend on the pixel to the left: sequential
-            cur = np.zeros(stride, np.int32)
-            ln, pv = line.tolist(), prev.tolist()
-            c = [0] * stride
-            for i in range(stride):
-                a = c[i - bpp] if i >= bpp else 0
-                b = pv[i]
-                if ft == 3:
-                    c[i] = (ln[i] + ((a + b) >> 1)) & 255
-                else:
-                    cc = pv[i - bpp] if i >= bpp else 0
-                    c[i] = (ln[i] + _paeth(a, b, cc)) & 255
-            cur = np.array(c, np.int32)
-        else:
-            raise ValueError(f"PNG filter type {ft}")
-        out[y] = cur.astype(np.uint8)
-        prev = cur
-    return out.reshape(h, w, 3) if bpp == 3 else out.reshape(h, w)
+    return w, h, bpp, raw
+
+
+def unfilter(raw, w, h, bpp):
+    """Filtered scanlines (h rows of 1 + w*bpp bytes) -> uint8 (h, w, bpp): the five PNG filter types mod 256,
+    row 0 over a zero previous row, pixel 0 with zero left and upper-left neighbours. Average and Paeth are
+    recurrences along the row that also read the row above, so the image is swept by anti-diagonals
+    (pixel x of row r at step r + x: its left, upper and upper-left neighbours are done) with every row of a
+    diagonal handled at once, the schedule of the HIP kernel (csrc/ingest.hip)."""
+    lines = np.frombuffer(raw, np.uint8, h * (w * bpp + 1)).reshape(h, w * bpp + 1)
+    ft = lines[:, 0].astype(np.int32)
+    if ft.size and int(ft.max()) > 4:
+        raise ValueError(f"PNG filter type {int(ft.max())}")
+    x_in = lines[:, 1:].reshape(h, w, bpp).astype(np.int32)
+    if not np.any(ft >= 3):  # no recurrence on the row above's left neighbour: whole rows at a time
+        out = np.zeros((h, w, bpp), np.int32)
+        prev = np.zeros((w, bpp), np.int32)
+        for y in range(h):
+            if ft[y] == 0:
+                cur = x_in[y]
+            elif ft[y] == 2:
+                cur = (x_in[y] + prev) & 255
+            else:  # Sub: a running sum per channel
+                cur = np.cumsum(x_in[y], axis=0) & 255
+            out[y] = cur
+            prev = cur
+        return out.astype(np.uint8)
+    o = np.zeros((h + 1, w + 1, bpp), np.int32)  # one zero row above and one zero column to the left
+    for d in range(h + w - 1):
+        r = np.arange(max(0, d - w + 1), min(h - 1, d) + 1)
+        x = d - r
+        a, b, c = o[r + 1, x], o[r, x + 1], o[r, x]
+        f = ft[r][:, None]
+        p = a + b - c
+        pa, pb, pc = np.abs(p - a), np.abs(p - b), np.abs(p - c)
+        paeth = np.where((pa <= pb) & (pa <= pc), a, np.where(pb <= pc, b, c))
+        pred = np.where(f == 1, a, np.where(f == 2, b, np.where(f == 3, (a + b) >> 1, np.where(f == 4, paeth, 0))))
+        o[r + 1, x + 1] = (x_in[r, x] + pred) & 255
+    return o[1:, 1:].astype(np.uint8)
+
+
+def decode_png(data):
+    """-> uint8 array (H, W, 3) RGB, (H, W) grey, (H, W, 4) RGBA or (H, W, 2) grey + alpha. 8 bits per
+    channel, the five filter types, no interlace."""
+    w, h, bpp, raw = inflate_png(data)
+    out = unfilter(raw, w, h, bpp)
+    return out[:, :, 0] if bpp == 1 else out
 
 
 def read_png(path):

@@ -12,7 +12,8 @@ Cameras: --synthetic N takes the synthetic scene of deformgs/train.py (N Gaussia
 holds no saved model yet, the scene's own initial Gaussians and a fresh network (heads at 1/100 scale) are
 saved there as iteration 0 first, so the script runs with no dataset. -s SOURCE reads a D-NeRF style
 transforms_train.json / transforms_test.json (camera_angle_x, per frame transform_matrix and time;
-dataset_readers.py:222-262) for the cameras; ground-truth images are written only for views that carry one.
+dataset_readers.py:222-262) for the cameras; a view whose image file exists carries it as ground truth (composited
+over the chosen background and resized to --res by deformgs/ingest.py), and gt/ is written for those views.
 """
 import argparse
 import json
@@ -33,12 +34,26 @@ class _Set:
         self.train, self.test = train, test
 
 
-def read_transforms(source, width, height, device):
-    """D-NeRF transforms_{train,test}.json -> _Set of Cameras without images (dataset_readers.py:222-262)."""
+def attach_images(cams, paths, white_background, width, height, device):
+    """Views whose image file exists get original_image: composited over the background and resized to the
+    render size by deformgs/ingest.py (byte / 255, which render_set's 8-bit gt/ write maps back to the same
+    byte). The others stay without one."""
+    from .ingest import ingest_images
+    have = [i for i, p in enumerate(paths) if p and os.path.isfile(p)]
+    if not have:
+        return
+    images = ingest_images([paths[i] for i in have], white_background, size=(width, height), device=device)
+    for k, i in enumerate(have):
+        cams[i].original_image = images[k]
+
+
+def read_transforms(source, width, height, device, white_background=False, extension=".png"):
+    """D-NeRF transforms_{train,test}.json -> _Set of Cameras (dataset_readers.py:222-262); a view carries its
+    ground-truth image when the frame's file exists under `source`."""
     sets = {}
     for name in ("train", "test"):
         path = os.path.join(source, f"transforms_{name}.json")
-        cams = []
+        cams, files = [], []
         if os.path.exists(path):
             with open(path) as f:
                 meta = json.load(f)
@@ -51,6 +66,8 @@ def read_transforms(source, width, height, device):
                 # dataset_readers.py:260-262 swaps the names: FovY = fovx, FovX = fovy
                 cams.append(Camera(R, T, FoVx=fovy, FoVy=fovx, width=width, height=height, fid=fid, uid=k,
                                    data_device=device))
+                files.append(os.path.join(source, fr["file_path"] + extension) if "file_path" in fr else None)
+            attach_images(cams, files, white_background, width, height, device)
         sets[name] = cams
     return _Set(sets["train"], sets["test"])
 
@@ -85,7 +102,7 @@ def load_scene(args, device="cuda"):
                     head.bias.mul_(0.01)
             d0.save_weights(args.model_path, 0)
     elif args.source_path:
-        cams = read_transforms(args.source_path, W, H, dev)
+        cams = read_transforms(args.source_path, W, H, dev, white_background=args.white_background)
     else:
         raise SystemExit("render_cli: give the cameras with --synthetic N or -s SOURCE (transforms_*.json)")
     it = _iteration(args.model_path, args.iteration)

@@ -310,12 +310,8 @@ class SyntheticScene:
         return gaussians
 
 
-def main(argv=None):
-    """Synthetic-scene training run with the reference's defaults (config 3: a full train loop);
-    prints one JSON line: iters/s over the whole loop (densification, reports and Adam included), the
-    reference's fwd+bwd span per iteration, the final Gaussian count and the test PSNR."""
+def build_parser():
     import argparse
-    import json
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=55_000)
     ap.add_argument("--res", type=int, default=800)
@@ -329,7 +325,27 @@ def main(argv=None):
     ap.add_argument("--6dof", dest="six_dof", action="store_true")
     ap.add_argument("--test-every", type=int, default=0)
     ap.add_argument("--no-deferred", action="store_true")
-    args = ap.parse_args(argv)
+    # a dataset directory (deformgs/dataset.py) instead of the synthetic scene: the reference's flags
+    ap.add_argument("--source_path", "-s", default="")
+    ap.add_argument("--model_path", "-m", default="")
+    ap.add_argument("--eval", action="store_true")
+    ap.add_argument("--resolution", "-r", type=int, default=-1)
+    ap.add_argument("--white_background", action="store_true")
+    ap.add_argument("--init_points", type=int, default=100_000)
+    ap.add_argument("--save_iterations", type=int, nargs="+", default=[])
+    ap.add_argument("--test_iterations", type=int, nargs="+", default=[])
+    ap.add_argument("--is_6dof", action="store_true")
+    return ap
+
+
+def main(argv=None):
+    """Training run with the reference's defaults; prints one JSON line: iters/s over the whole loop
+    (densification, reports and Adam included), the reference's fwd+bwd span per iteration, the final
+    Gaussian count and the test PSNR. Without -s: the synthetic scene (config 3: a full train loop). With
+    -s SOURCE -m MODEL: a D-NeRF dataset directory through deformgs/dataset.Scene; the model is saved at
+    --save_iterations and at the last iteration."""
+    import json
+    args = build_parser().parse_args(argv)
     from .dist import init_from_env
     from .gaussian_model import GaussianModel
     rank, world, local = init_from_env()
@@ -341,21 +357,41 @@ def main(argv=None):
         if v is not None:
             kw[k] = v
     opt = OptimizationParams(**kw)
-    dataset = ModelParams(is_blender=not args.non_blender, is_6dof=args.six_dof)
-    scene = SyntheticScene(args.n, args.res, args.res, device=dev)
-    g = scene.init_gaussians(GaussianModel(3))
     tests = list(range(args.test_every, args.iterations + 1, args.test_every)) if args.test_every else [args.iterations]
+    if args.source_path:
+        if not args.model_path:
+            raise SystemExit("train: -s SOURCE needs -m MODEL (where input.ply, cameras.json and the model are written)")
+        from .dataset import Scene
+        dataset = ModelParams(is_blender=not args.non_blender, is_6dof=args.six_dof or args.is_6dof,
+                              white_background=args.white_background, source_path=args.source_path,
+                              model_path=args.model_path, eval=args.eval, resolution=args.resolution,
+                              init_points=args.init_points, data_device=str(dev))
+        g = GaussianModel(dataset.sh_degree)
+        scene = Scene(dataset, g)
+        tests = sorted(set(args.test_iterations)) or tests
+        saves = sorted(set(args.save_iterations) | {args.iterations})
+        cam0 = scene.getTrainCameras()[0]
+        what = (f"{g.get_xyz.shape[0]} Gaussians init, {len(scene.getTrainCameras())} views of {args.source_path} @ "
+                f"{cam0.image_width}x{cam0.image_height}")
+    else:
+        dataset = ModelParams(is_blender=not args.non_blender, is_6dof=args.six_dof or args.is_6dof)
+        scene = SyntheticScene(args.n, args.res, args.res, device=dev)
+        g = scene.init_gaussians(GaussianModel(3))
+        saves = []
+        what = f"{args.n} Gaussians init @ {args.res}x{args.res}"
     torch.manual_seed(0)
-    hist = training(dataset, opt, PipelineParams(), tests, [], scene, g, deferred_count=not args.no_deferred,
+    hist = training(dataset, opt, PipelineParams(), tests, saves, scene, g, deferred_count=not args.no_deferred,
+                    model_path=args.model_path or None,
                     log=(lambda s: print(s, flush=True)) if rank == 0 else None)
     fb = float(np.median(hist["iter_ms"])) if hist["iter_ms"] else 0.0
-    out = {"metric": f"train iters/s (full loop: densify + Adam + reports), {args.n} Gaussians init @ "
-                     f"{args.res}x{args.res}", "value": args.iterations * world / hist["wall_s"], "unit": "iters/s",
+    out = {"metric": f"train iters/s (full loop: densify + Adam + reports), {what}",
+           "value": args.iterations * world / hist["wall_s"], "unit": "iters/s",
            "n_gpus": world, "iterations": args.iterations, "fwd_bwd_ms_median": fb,
            "final_gaussians": hist["n"][-1], "redone_iterations": int(sum(hist["redone"])),
            "report": {str(k): v for k, v in hist["report"].items()}, "final_loss": hist["loss"][-1]}
     if rank == 0:
         print(json.dumps(out), flush=True)
+    return out
 
 
 if __name__ == "__main__":

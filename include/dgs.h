@@ -421,6 +421,26 @@ typedef struct dgs_render_frames_args {
 } dgs_render_frames_args;
 int dgs_render_frames(const dgs_render_frames_args *a, int *redone_frames, void *stream);
 
+/* ---- dataset image ingest (scene/dataset_readers.py:242-255 + utils/general_utils.py:23-29) ----
+ * The host parses the PNG chunks, inflates and validates (stream length, every filter byte <= 4); the
+ * device does the rest, in stream order.
+ * dgs_ingest_unfilter: scanlines = B images of H x (1 + W*bpp) still-filtered bytes (bpp 3 or 4, 8-bit,
+ * non-interlaced), one wave per image. The five PNG filter types are undone mod 256 (row 0: zero previous
+ * row; pixel 0: zero left / upper-left); a filter byte above 4 is treated as 0. lut NULL: out = (B,H,W,bpp)
+ * bytes. lut (bpp 4 only): the 256 x 256 table [colour][alpha] of the reader's composite over its background
+ * (built by the caller in float64); out = (B,H,W,3). W <= 8192 (DGS_ERR_UNSUPPORTED beyond).
+ * dgs_ingest_resample: one pass of PIL's Image.resize default (bicubic a = -0.5, antialiased, 8 bits per
+ * channel) along the middle axis of in (outer, n_in, inner) -> out (outer, n_out, inner). bounds: (n_out, 2)
+ * ints = first input index, tap count; coef: (n_out, ksize) ints = normalised weights in 22-bit fixed
+ * point; out = clip8((2^21 + sum in * coef) >> 22). Horizontal pass of (B,H,W,3): outer B*H, inner 3;
+ * vertical: outer B, inner w*3.
+ * dgs_ingest_to_float: (B,H,W,3) bytes -> (B,3,H,W) float32 = byte / 255 (Camera.original_image). */
+int dgs_ingest_unfilter(int B, int W, int H, int bpp, const uint8_t *scanlines, const uint8_t *lut, uint8_t *out,
+                        void *stream);
+int dgs_ingest_resample(int64_t outer, int n_in, int n_out, int inner, const uint8_t *in, const int *bounds,
+                        const int *coef, int ksize, uint8_t *out, void *stream);
+int dgs_ingest_to_float(int B, int H, int W, const uint8_t *rgb8, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,118 @@
+"""Dataset image ingest timing: 150 RGBA PNGs at 800x800 (a D-NeRF scene's worth), built in memory.
+
+The images are rendered-looking frames (tests/png_fixtures.disc_image; --distinct of them, repeated), encoded
+with adaptive per-row filters (the libpng heuristic), so Paeth and Average rows dominate as in real renders.
+Timed, medians of --rounds rounds, the legs alternating within a round:
+  (a) host inflate + validation, at most 16 threads (deformgs.ingest.inflate_all)
+  (b) upload + HIP ingest to the float images at 800^2 and at 400^2 (ends in a device synchronise)
+  (c) the numpy path on 5 of the images, scaled to the full count
+  (d) where PIL is importable: the reference's pipeline per image: Image.open().convert("RGBA"), the float64
+      composite, resize, / 255 (scene/dataset_readers.py:242-255, utils/general_utils.py:23-29), at 400^2
+Prints one JSON line per leg and a summary line; --out appends them to a file (profiles/ingest_time.jsonl).
+"""
+import argparse
+import io
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (os.path.join(ROOT, "deformable-3d-gaussians_amd"), os.path.join(ROOT, "tests")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+from png_fixtures import adaptive_types, disc_image, encode_png_filtered  # noqa: E402
+
+from deformgs import ingest  # noqa: E402
+
+
+def build_images(n, res, distinct):
+    frames = []
+    hist = np.zeros(5, np.int64)
+    for k in range(distinct):
+        img = disc_image(res, res, k / distinct, n_discs=6, seed=1)
+        types = adaptive_types(img)
+        hist += np.bincount(types, minlength=5)
+        frames.append(encode_png_filtered(img, types))
+    return [frames[i % distinct] for i in range(n)], hist
+
+
+def reference_pipeline(data, size):
+    from PIL import Image
+    im_data = np.array(Image.open(io.BytesIO(data)).convert("RGBA"))
+    bg = np.array([0, 0, 0])
+    norm_data = im_data / 255.0
+    arr = norm_data[:, :, :3] * norm_data[:, :, 3:4] + bg * (1 - norm_data[:, :, 3:4])
+    image = Image.fromarray((arr * 255.0).astype(np.uint8), "RGB")
+    return torch.from_numpy(np.array(image.resize(size))) / 255.0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--images", type=int, default=150)
+    ap.add_argument("--res", type=int, default=800)
+    ap.add_argument("--distinct", type=int, default=10)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--out", default="")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "ingest_time.py measures the GPU path: it needs a GPU"
+    dev = torch.device("cuda", 0)
+    n, R = args.images, args.res
+    pngs, hist = build_images(n, R, args.distinct)
+    try:
+        import PIL  # noqa: F401
+        have_pil = True
+    except ImportError:
+        have_pil = False
+    metas = ingest.inflate_all(pngs)
+    raws = [m[3] for m in metas]
+    # warm-up of every timed shape; the small result is also checked against the numpy path
+    for size in ((R, R), (R // 2, R // 2)):
+        f, _ = ingest.ingest_group_device(raws[:8], R, R, 4, False, size, dev)
+        torch.cuda.synchronize()
+    want = ingest.ingest_group_numpy(raws[:1], R, R, 4, False, (R // 2, R // 2))[0]
+    assert np.array_equal(f[:1].cpu().numpy(), want), "HIP ingest differs from the numpy path"
+    t = {k: [] for k in ("inflate", "hip_full", "hip_half", "numpy_half", "pil_half")}
+    for _ in range(args.rounds):
+        t0 = time.perf_counter()
+        ingest.inflate_all(pngs)
+        t["inflate"].append(time.perf_counter() - t0)
+        for key, size in (("hip_full", (R, R)), ("hip_half", (R // 2, R // 2))):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            f, _ = ingest.ingest_group_device(raws, R, R, 4, False, size, dev)
+            torch.cuda.synchronize()
+            t[key].append(time.perf_counter() - t0)
+            del f
+        t0 = time.perf_counter()
+        ingest.ingest_group_numpy(raws[:5], R, R, 4, False, (R // 2, R // 2))
+        t["numpy_half"].append((time.perf_counter() - t0) * n / 5)
+        if have_pil:
+            t0 = time.perf_counter()
+            for d in pngs:
+                reference_pipeline(d, (R // 2, R // 2))
+            t["pil_half"].append(time.perf_counter() - t0)
+    lines = []
+    for k, v in t.items():
+        if v:
+            lines.append({"leg": k, "images": n, "res": R, "seconds_median": statistics.median(v), "seconds": v})
+    med = {d["leg"]: d["seconds_median"] for d in lines}
+    lines.append({"summary": "inflate + hip_half vs pil_half", "hip_total_s": med["inflate"] + med["hip_half"],
+                  "pil_s": med.get("pil_half"), "filter_rows": {str(i): int(c) for i, c in enumerate(hist)},
+                  "device": torch.cuda.get_device_name(0), "filtered_bytes": sum(len(r) for r in raws)})
+    for d in lines:
+        print(json.dumps(d), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as f:
+            for d in lines:
+                f.write(json.dumps(d) + "\n")
+
+
+if __name__ == "__main__":
+    main()
