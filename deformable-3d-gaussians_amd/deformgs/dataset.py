@@ -1,4 +1,5 @@
-"""D-NeRF (Blender-style) dataset directories: the counterpart of scene.Scene / readNerfSyntheticInfo.
+"""Dataset directories: the counterpart of scene.Scene with the D-NeRF (Blender-style) reader
+readNerfSyntheticInfo and the Nerfies-format reader readNerfiesInfo (NeRF-DS, HyperNeRF vrig / interp / misc).
 
 Mirrors (file:line in the reference):
   scene/dataset_readers.py:223-266  readCamerasFromTransforms: R / T from transform_matrix, fid = frame["time"],
@@ -6,21 +7,30 @@ Mirrors (file:line in the reference):
                                     the swap is kept, as deformgs/render_cli.read_transforms does)
   scene/dataset_readers.py:269-306  readNerfSyntheticInfo: test merged into train unless eval; getNerfppNorm;
                                     points3d.ply or 100 000 random points in [-1.3, 1.3]^3
+  scene/dataset_readers.py:398-473  readNerfiesCameras: scene.json / metadata.json / dataset.json, the split rule
+                                    keyed on the name of SOURCE's parent directory, fid = time_id / max time_id,
+                                    one camera/<id>.json per view, rgb/<int(1/ratio)>x/<id>.png
+  scene/dataset_readers.py:476-509  readNerfiesInfo: the first train_num cameras train and the rest test with
+                                    eval; points3d.ply or points.npy as (xyz - center) * scale
+  utils/camera_utils.py:92-112      camera_nerfies_from_JSON: focal_length * ratio, the old `tangential` key
   scene/dataset_readers.py:77-98    getNerfppNorm: translate = -mean camera centre, radius = 1.1 x largest
                                     distance from it
   utils/camera_utils.py:21-44       loadCam's resolution rule (target_resolution)
   utils/camera_utils.py:69-89       camera_to_JSON
-  scene/__init__.py:23-112          Scene: input.ply, cameras.json, the camera lists, create_from_pcd
+  scene/__init__.py:23-112          Scene: the format dispatch, input.ply, cameras.json, the camera lists,
+                                    create_from_pcd
 
 The images go through deformgs/ingest.py (HIP unfilter + composite + resize on a GPU device), one batch per
-camera set; every camera's original_image is a view into that batch.
+camera set; every camera's original_image is a view into that batch. The Nerfies reader needs only what the
+reference's needs: JSON, points.npy and 8-bit RGB PNGs, whose size comes from the file header (png_size).
 
-Deviation: the reference writes the random point cloud into the dataset directory (points3d.ply). Here SOURCE
+Deviation: the reference writes a generated point cloud into the dataset directory (points3d.ply). Here SOURCE
 is read only; the cloud is written as MODEL/input.ply, where the reference copies it anyway, and a later run
-draws the same cloud again from its seed.
+builds the same cloud again (the colours from a seeded generator).
 
-Out of scope (they need cv2 / imageio behaviour): the NeRF-DS / Nerfies / HyperNeRF, Colmap, DTU and
-plenoptic readers; gt_alpha_mask and load2gpu_on_the_fly.
+Out of scope: the DTU reader (it needs cv2 / imageio behaviour), the Colmap and plenoptic readers (their images
+are JPEG) and the Dynamic-360 one; gt_alpha_mask and load2gpu_on_the_fly. Scene names such a directory in its
+ValueError.
 """
 import json
 import os
@@ -170,6 +180,135 @@ def read_nerf_synthetic(path, white_background, eval, extension=".png", init_poi
     return SceneInfo(point_cloud=pcd, train_cameras=train, test_cameras=test, nerf_normalization=norm, ply_path=ply_path)
 
 
+NERFIES_KINDS = ("vrig", "nerf", "interp", "other")
+
+
+def nerfies_kind_of(path):
+    """dataset_readers.py:409-430: the split branch from the name of SOURCE's parent directory, taken from the
+    absolute, normalised path (a trailing slash or a relative path does not change the answer)."""
+    name = os.path.basename(os.path.dirname(os.path.abspath(path)))
+    if name.startswith("vrig"):
+        return "vrig"
+    if name.startswith("NeRF") or name.startswith("nerf"):
+        return "nerf"
+    if name.startswith("interp") or name.startswith("hyper"):
+        return "interp"
+    return "other"
+
+
+def camera_nerfies_from_json(path, scale):
+    """camera_utils.py:92-112. Principal point, skew and distortion are read and, as upstream, used nowhere."""
+    with open(path) as f:
+        camera_json = json.load(f)
+    if "tangential" in camera_json:  # old camera JSON
+        camera_json["tangential_distortion"] = camera_json["tangential"]
+    return dict(orientation=np.array(camera_json["orientation"]), position=np.array(camera_json["position"]),
+                focal_length=camera_json["focal_length"] * scale,
+                principal_point=np.array(camera_json["principal_point"]) * scale, skew=camera_json["skew"],
+                pixel_aspect_ratio=camera_json["pixel_aspect_ratio"],
+                radial_distortion=np.array(camera_json["radial_distortion"]),
+                tangential_distortion=np.array(camera_json["tangential_distortion"]))
+
+
+def read_nerfies_cameras(path, nerfies_kind=None):
+    """dataset_readers.py:398-473 without the image load. nerfies_kind: one of NERFIES_KINDS to choose the split
+    branch explicitly; None applies the directory-name rule. -> (CameraInfos, train then val; train_num; scene
+    centre; scene scale)."""
+    kind = nerfies_kind or nerfies_kind_of(path)
+    if kind not in NERFIES_KINDS:
+        raise ValueError(f"nerfies_kind {kind!r}: one of {', '.join(NERFIES_KINDS)}")
+    with open(os.path.join(path, "scene.json")) as f:
+        scene_json = json.load(f)
+    with open(os.path.join(path, "metadata.json")) as f:
+        meta_json = json.load(f)
+    with open(os.path.join(path, "dataset.json")) as f:
+        dataset_json = json.load(f)
+    coord_scale = scene_json["scale"]
+    scene_center = scene_json["center"]
+    if kind in ("vrig", "nerf"):
+        train_img = dataset_json["train_ids"]
+        all_img = train_img + dataset_json["val_ids"]
+        ratio = 0.25 if kind == "vrig" else 1.0
+    elif kind == "interp":
+        train_img = dataset_json["ids"][::4]
+        all_img = train_img + dataset_json["ids"][2::4]
+        ratio = 0.5
+    else:
+        train_img = dataset_json["ids"][::4]
+        all_img = train_img
+        ratio = 0.5
+    max_time = max(meta_json[i]["time_id"] for i in all_img)
+    infos = []
+    for idx, im in enumerate(all_img):
+        camera = camera_nerfies_from_json(os.path.join(path, "camera", f"{im}.json"), ratio)
+        position = (camera["position"] - scene_center) * coord_scale
+        image_path = os.path.join(path, "rgb", f"{int(1 / ratio)}x", f"{im}.png")
+        width, height = png_size(image_path)
+        R = camera["orientation"].T
+        T = -position @ R
+        focal = camera["focal_length"]
+        infos.append(CameraInfo(uid=idx, R=R, T=T, FovY=focal2fov(focal, height), FovX=focal2fov(focal, width),
+                                image_path=image_path, image_name=os.path.splitext(os.path.basename(image_path))[0],
+                                width=width, height=height, fid=meta_json[im]["time_id"] / max_time))
+    return infos, len(train_img), scene_center, coord_scale
+
+
+def read_nerfies(path, eval, model_path=None, nerfies_kind=None, seed=0):
+    """dataset_readers.py:476-509. The point cloud is SOURCE/points3d.ply if present; otherwise points.npy as
+    (xyz - center) * scale with colours SH2RGB(U[0, 1) / 255) from a seeded generator, written to
+    MODEL/input.ply when model_path is given (never under SOURCE) and read back from there, so the colours
+    carry the file's 8-bit rounding as upstream."""
+    cams, train_num, scene_center, scene_scale = read_nerfies_cameras(path, nerfies_kind)
+    train, test = (cams[:train_num], cams[train_num:]) if eval else (cams, [])
+    norm = nerfpp_norm(train)
+    ply_path = os.path.join(path, "points3d.ply")
+    npy_path = os.path.join(path, "points.npy")
+    if os.path.exists(ply_path):
+        pcd = fetch_ply(ply_path)
+    elif os.path.exists(npy_path):
+        xyz = (np.load(npy_path) - scene_center) * scene_scale
+        rgb = np.random.default_rng(seed).random((xyz.shape[0], 3)) / 255.0 * C0 + 0.5
+        ply_path = None
+        if model_path:
+            os.makedirs(model_path, exist_ok=True)
+            ply_path = os.path.join(model_path, "input.ply")
+            store_ply(ply_path, xyz, rgb * 255)
+            pcd = fetch_ply(ply_path)
+        else:
+            pcd = BasicPointCloud(points=xyz.astype(np.float32), colors=(rgb * 255).astype(np.uint8) / 255.0,
+                                  normals=np.zeros((xyz.shape[0], 3)))
+    else:
+        raise ValueError(f"{path}: neither points3d.ply nor points.npy (a Nerfies dataset brings its point cloud)")
+    return SceneInfo(point_cloud=pcd, train_cameras=train, test_cameras=test, nerf_normalization=norm, ply_path=ply_path)
+
+
+# scene/__init__.py:45-63 in its order: marker file or directory -> the format it announces
+_FORMAT_MARKERS = (("sparse", "Colmap"), ("transforms_train.json", "D-NeRF"), ("cameras_sphere.npz", "DTU"),
+                   ("dataset.json", "Nerfies"), ("poses_bounds.npy", "plenoptic video (Neu3D)"),
+                   ("transforms.json", "Dynamic-360"))
+
+
+def dataset_format(source_path):
+    """"D-NeRF" or "Nerfies" by the reference's dispatch order; ValueError for the formats it also knows but
+    this package does not read, and for a directory it would not recognise either."""
+    for marker, name in _FORMAT_MARKERS:
+        if os.path.exists(os.path.join(source_path, marker)):
+            if name in ("D-NeRF", "Nerfies"):
+                return name
+            raise ValueError(f"{source_path}: found {marker}, a {name} dataset: that format is unsupported "
+                             "(D-NeRF and Nerfies directories are read)")
+    raise ValueError(f"{source_path}: could not recognise the scene type (no transforms_train.json of a D-NeRF "
+                     "directory and no dataset.json of a Nerfies one)")
+
+
+def read_scene_info(source_path, white_background, eval, init_points=100_000, model_path=None, nerfies_kind=None):
+    """The reader of the directory's format (dataset_format). init_points only applies to D-NeRF directories:
+    a Nerfies one starts from its own point cloud."""
+    if dataset_format(source_path) == "Nerfies":
+        return read_nerfies(source_path, eval, model_path=model_path, nerfies_kind=nerfies_kind)
+    return read_nerf_synthetic(source_path, white_background, eval, init_points=init_points, model_path=model_path)
+
+
 def target_resolution(orig_w, orig_h, resolution):
     """camera_utils.py:24-42 at resolution_scale 1: -r in {1, 2, 4, 8} -> round(orig / r) per axis (Python's
     round: halves go to even); -1 -> full size unless wider than 1600; anything else is a target width."""
@@ -213,8 +352,10 @@ def load_cameras(cam_infos, resolution, white_background, device):
 
 
 class Scene:
-    """scene/__init__.py:23-112 for a D-NeRF directory. args: source_path, model_path, white_background, eval,
-    resolution (default -1), init_points (default 100 000), data_device (default "cuda")."""
+    """scene/__init__.py:23-112 for a D-NeRF or a Nerfies directory (dataset_format). args: source_path,
+    model_path, white_background, eval, resolution (default -1), init_points (default 100 000; D-NeRF only),
+    nerfies_kind (default None: the directory-name rule), data_device (default "cuda"). white_background has
+    no effect on RGB images (Nerfies captures carry no alpha)."""
 
     def __init__(self, args, gaussians, load_iteration=None):
         from .deform_model import searchForMaxIteration
@@ -224,13 +365,13 @@ class Scene:
         if load_iteration is not None:
             self.loaded_iter = (searchForMaxIteration(os.path.join(self.model_path, "point_cloud"))
                                 if load_iteration == -1 else load_iteration)
-        if not os.path.exists(os.path.join(args.source_path, "transforms_train.json")):
-            raise ValueError(f"{args.source_path}: no transforms_train.json (only D-NeRF style datasets are read)")
+        self.format = dataset_format(args.source_path)  # raises on what is not read, before MODEL is created
         device = torch.device(getattr(args, "data_device", "cuda"))
         os.makedirs(self.model_path, exist_ok=True)
-        info = read_nerf_synthetic(args.source_path, args.white_background, args.eval,
-                                   init_points=getattr(args, "init_points", 100_000),
-                                   model_path=None if self.loaded_iter else self.model_path)
+        info = read_scene_info(args.source_path, args.white_background, args.eval,
+                               init_points=getattr(args, "init_points", 100_000),
+                               model_path=None if self.loaded_iter else self.model_path,
+                               nerfies_kind=getattr(args, "nerfies_kind", None))
         if not self.loaded_iter:
             dest = os.path.join(self.model_path, "input.ply")
             if info.ply_path != dest:  # SOURCE/points3d.ply: copied, as upstream

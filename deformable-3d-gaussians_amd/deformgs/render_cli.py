@@ -14,6 +14,10 @@ saved there as iteration 0 first, so the script runs with no dataset. -s SOURCE 
 transforms_train.json / transforms_test.json (camera_angle_x, per frame transform_matrix and time;
 dataset_readers.py:222-262) for the cameras; a view whose image file exists carries it as ground truth (composited
 over the chosen background and resized to --res by deformgs/ingest.py), and gt/ is written for those views.
+-s SOURCE at a Nerfies directory (dataset.json: NeRF-DS / HyperNeRF) takes both sets from the training reader
+(deformgs/dataset.read_nerfies_cameras: train ids, then val ids as the test set): cameras, frame times and
+ground-truth images from the files; without --res the frame size is the dataset's own after -r, the training
+size.
 """
 import argparse
 import json
@@ -72,6 +76,23 @@ def read_transforms(source, width, height, device, white_background=False, exten
     return _Set(sets["train"], sets["test"])
 
 
+def read_nerfies_sets(source, res, resolution, device, nerfies_kind=None):
+    """A Nerfies directory -> _Set of Cameras with their ground truth, split as the training reader splits it with
+    --eval. res None: the files' size after the -r rule (dataset.load_cameras); (W, H): that frame size."""
+    from .dataset import load_cameras, read_nerfies_cameras
+    infos, train_num, _, _ = read_nerfies_cameras(source, nerfies_kind)
+    sets = []
+    for part in (infos[:train_num], infos[train_num:]):
+        if res is None:
+            sets.append(load_cameras(part, resolution, False, device))
+            continue
+        cams = [Camera(c.R, c.T, FoVx=c.FovX, FoVy=c.FovY, width=res[0], height=res[1], fid=c.fid, uid=k,
+                       data_device=device) for k, c in enumerate(part)]
+        attach_images(cams, [c.image_path for c in part], False, res[0], res[1], device)
+        sets.append(cams)
+    return _Set(*sets)
+
+
 def _iteration(model_path, iteration):
     from .deform_model import searchForMaxIteration
     if iteration >= 0:
@@ -84,7 +105,7 @@ def load_scene(args, device="cuda"):
     from .deform_model import DeformModelBaseline
     from .gaussian_model import GaussianModel
     dev = torch.device(device)
-    W, H = args.res
+    W, H = args.res or (800, 800)
     if args.synthetic:
         from .train import SyntheticScene
         scene = SyntheticScene(args.synthetic, W, H, device=dev, white_background=args.white_background)
@@ -101,6 +122,9 @@ def load_scene(args, device="cuda"):
                     head.weight.mul_(0.01)
                     head.bias.mul_(0.01)
             d0.save_weights(args.model_path, 0)
+    elif args.source_path and os.path.exists(os.path.join(args.source_path, "dataset.json")) and not os.path.exists(
+            os.path.join(args.source_path, "transforms_train.json")):
+        cams = read_nerfies_sets(args.source_path, args.res, args.resolution, dev, args.nerfies_kind)
     elif args.source_path:
         cams = read_transforms(args.source_path, W, H, dev, white_background=args.white_background)
     else:
@@ -162,7 +186,10 @@ def build_parser():
     ap.add_argument("--skip_train", action="store_true")
     ap.add_argument("--skip_test", action="store_true")
     ap.add_argument("--synthetic", type=int, default=0, metavar="N")
-    ap.add_argument("--res", type=int, nargs=2, default=[800, 800], metavar=("W", "H"))
+    ap.add_argument("--res", type=int, nargs=2, default=None, metavar=("W", "H"),
+                    help="frame size (default 800 800; for a Nerfies SOURCE the dataset's own size after -r)")
+    ap.add_argument("--resolution", "-r", type=int, default=-1, help="the training script's -r (Nerfies SOURCE)")
+    ap.add_argument("--nerfies_kind", choices=["vrig", "nerf", "interp", "other"], default=None)
     ap.add_argument("--frames", type=int, default=None, help="frames of an interpolation mode (default: the reference's)")
     ap.add_argument("--view_index", type=int, default=-1, help="the fixed view of time / view / all / pose (-1: random)")
     ap.add_argument("--sh_degree", type=int, default=3)

@@ -335,6 +335,8 @@ def build_parser():
     ap.add_argument("--save_iterations", type=int, nargs="+", default=[])
     ap.add_argument("--test_iterations", type=int, nargs="+", default=[])
     ap.add_argument("--is_6dof", action="store_true")
+    ap.add_argument("--nerfies_kind", choices=["vrig", "nerf", "interp", "other"], default=None,
+                    help="split rule of a Nerfies directory (default: from the name of SOURCE's parent directory)")
     return ap
 
 
@@ -342,8 +344,9 @@ def main(argv=None):
     """Training run with the reference's defaults; prints one JSON line: iters/s over the whole loop
     (densification, reports and Adam included), the reference's fwd+bwd span per iteration, the final
     Gaussian count and the test PSNR. Without -s: the synthetic scene (config 3: a full train loop). With
-    -s SOURCE -m MODEL: a D-NeRF dataset directory through deformgs/dataset.Scene; the model is saved at
-    --save_iterations and at the last iteration."""
+    -s SOURCE -m MODEL: a D-NeRF or Nerfies (NeRF-DS / HyperNeRF) dataset directory through
+    deformgs/dataset.Scene; the model is saved at --save_iterations and at the last iteration. The network is
+    the user's choice for either format (--non-blender, as --is_blender upstream)."""
     import json
     args = build_parser().parse_args(argv)
     from .dist import init_from_env
@@ -361,11 +364,14 @@ def main(argv=None):
     if args.source_path:
         if not args.model_path:
             raise SystemExit("train: -s SOURCE needs -m MODEL (where input.ply, cameras.json and the model are written)")
-        from .dataset import Scene
+        from .dataset import Scene, dataset_format
+        if dataset_format(args.source_path) == "Nerfies" and not args.non_blender and rank == 0:
+            print(f"warning: {args.source_path} is a Nerfies directory trained with the blender network; "
+                  "real-world captures are meant for --non-blender", flush=True)
         dataset = ModelParams(is_blender=not args.non_blender, is_6dof=args.six_dof or args.is_6dof,
                               white_background=args.white_background, source_path=args.source_path,
                               model_path=args.model_path, eval=args.eval, resolution=args.resolution,
-                              init_points=args.init_points, data_device=str(dev))
+                              init_points=args.init_points, nerfies_kind=args.nerfies_kind, data_device=str(dev))
         g = GaussianModel(dataset.sh_degree)
         scene = Scene(dataset, g)
         tests = sorted(set(args.test_iterations)) or tests

@@ -1,4 +1,5 @@
-"""Dataset image ingest timing: 150 RGBA PNGs at 800x800 (a D-NeRF scene's worth), built in memory.
+"""Dataset image ingest timing: 150 RGBA PNGs at 800x800 (a D-NeRF scene's worth), built in memory; with
+--rgb --size 480 270, 150 RGB PNGs of a NeRF-DS capture's size (no alpha: no composite).
 
 The images are rendered-looking frames (tests/png_fixtures.disc_image; --distinct of them, repeated), encoded
 with adaptive per-row filters (the libpng heuristic), so Paeth and Average rows dominate as in real renders.
@@ -7,7 +8,10 @@ Timed, medians of --rounds rounds, the legs alternating within a round:
   (b) upload + HIP ingest to the float images at 800^2 and at 400^2 (ends in a device synchronise)
   (c) the numpy path on 5 of the images, scaled to the full count
   (d) where PIL is importable: the reference's pipeline per image: Image.open().convert("RGBA"), the float64
-      composite, resize, / 255 (scene/dataset_readers.py:242-255, utils/general_utils.py:23-29), at 400^2
+      composite, resize, / 255 (scene/dataset_readers.py:242-255, utils/general_utils.py:23-29), at 400^2;
+      with --rgb the Nerfies reader's: np.array(Image.open()), Image.fromarray, resize, / 255
+      (scene/dataset_readers.py:453-454)
+"full" and "half" are the file's size and half of it per axis (integer division).
 Prints one JSON line per leg and a summary line; --out appends them to a file (profiles/ingest_time.jsonl).
 """
 import argparse
@@ -31,19 +35,24 @@ from png_fixtures import adaptive_types, disc_image, encode_png_filtered  # noqa
 from deformgs import ingest  # noqa: E402
 
 
-def build_images(n, res, distinct):
+def build_images(n, width, height, distinct, rgb=False):
     frames = []
     hist = np.zeros(5, np.int64)
     for k in range(distinct):
-        img = disc_image(res, res, k / distinct, n_discs=6, seed=1)
+        img = disc_image(width, height, k / distinct, n_discs=6, seed=1)
+        if rgb:
+            img = np.ascontiguousarray(img[:, :, :3])
         types = adaptive_types(img)
         hist += np.bincount(types, minlength=5)
         frames.append(encode_png_filtered(img, types))
     return [frames[i % distinct] for i in range(n)], hist
 
 
-def reference_pipeline(data, size):
+def reference_pipeline(data, size, rgb=False):
     from PIL import Image
+    if rgb:
+        image = Image.fromarray(np.array(Image.open(io.BytesIO(data))).astype(np.uint8))
+        return torch.from_numpy(np.array(image.resize(size))) / 255.0
     im_data = np.array(Image.open(io.BytesIO(data)).convert("RGBA"))
     bg = np.array([0, 0, 0])
     norm_data = im_data / 255.0
@@ -56,14 +65,19 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=150)
     ap.add_argument("--res", type=int, default=800)
+    ap.add_argument("--size", type=int, nargs=2, default=None, metavar=("W", "H"), help="a non-square size instead of --res")
+    ap.add_argument("--rgb", action="store_true", help="RGB images (colour type 2), as real captures are")
     ap.add_argument("--distinct", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "ingest_time.py measures the GPU path: it needs a GPU"
     dev = torch.device("cuda", 0)
-    n, R = args.images, args.res
-    pngs, hist = build_images(n, R, args.distinct)
+    n = args.images
+    W, H = args.size or (args.res, args.res)
+    ch = 3 if args.rgb else 4
+    full, half = (W, H), (W // 2, H // 2)
+    pngs, hist = build_images(n, W, H, args.distinct, args.rgb)
     try:
         import PIL  # noqa: F401
         have_pil = True
@@ -72,37 +86,39 @@ def main():
     metas = ingest.inflate_all(pngs)
     raws = [m[3] for m in metas]
     # warm-up of every timed shape; the small result is also checked against the numpy path
-    for size in ((R, R), (R // 2, R // 2)):
-        f, _ = ingest.ingest_group_device(raws[:8], R, R, 4, False, size, dev)
+    for size in (full, half):
+        f, _ = ingest.ingest_group_device(raws[:8], W, H, ch, False, size, dev)
         torch.cuda.synchronize()
-    want = ingest.ingest_group_numpy(raws[:1], R, R, 4, False, (R // 2, R // 2))[0]
+    want = ingest.ingest_group_numpy(raws[:1], W, H, ch, False, half)[0]
     assert np.array_equal(f[:1].cpu().numpy(), want), "HIP ingest differs from the numpy path"
     t = {k: [] for k in ("inflate", "hip_full", "hip_half", "numpy_half", "pil_half")}
     for _ in range(args.rounds):
         t0 = time.perf_counter()
         ingest.inflate_all(pngs)
         t["inflate"].append(time.perf_counter() - t0)
-        for key, size in (("hip_full", (R, R)), ("hip_half", (R // 2, R // 2))):
+        for key, size in (("hip_full", full), ("hip_half", half)):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            f, _ = ingest.ingest_group_device(raws, R, R, 4, False, size, dev)
+            f, _ = ingest.ingest_group_device(raws, W, H, ch, False, size, dev)
             torch.cuda.synchronize()
             t[key].append(time.perf_counter() - t0)
             del f
         t0 = time.perf_counter()
-        ingest.ingest_group_numpy(raws[:5], R, R, 4, False, (R // 2, R // 2))
+        ingest.ingest_group_numpy(raws[:5], W, H, ch, False, half)
         t["numpy_half"].append((time.perf_counter() - t0) * n / 5)
         if have_pil:
             t0 = time.perf_counter()
             for d in pngs:
-                reference_pipeline(d, (R // 2, R // 2))
+                reference_pipeline(d, half, args.rgb)
             t["pil_half"].append(time.perf_counter() - t0)
     lines = []
     for k, v in t.items():
         if v:
-            lines.append({"leg": k, "images": n, "res": R, "seconds_median": statistics.median(v), "seconds": v})
+            lines.append({"leg": k, "images": n, "res": W if W == H else [W, H], "channels": ch,
+                          "seconds_median": statistics.median(v), "seconds": v})
     med = {d["leg"]: d["seconds_median"] for d in lines}
-    lines.append({"summary": "inflate + hip_half vs pil_half", "hip_total_s": med["inflate"] + med["hip_half"],
+    lines.append({"summary": "inflate + hip_half vs pil_half", "images": n, "res": W if W == H else [W, H], "channels": ch,
+                  "hip_total_s": med["inflate"] + med["hip_half"],
                   "pil_s": med.get("pil_half"), "filter_rows": {str(i): int(c) for i, c in enumerate(hist)},
                   "device": torch.cuda.get_device_name(0), "filtered_bytes": sum(len(r) for r in raws)})
     for d in lines:
