@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
+#include <atomic>
 #include <string>
 
 #include "../../include/dgs.h"
@@ -50,5 +52,27 @@ constexpr int TILE_Y = 16;
 constexpr int TILE_PIX = TILE_X * TILE_Y;
 
 __host__ __device__ inline int div_up(int a, int b) { return (a + b - 1) / b; }
+
+// the environment variable is set and its value starts with `c`
+inline bool env_starts(const char *name, char c) {
+    const char *e = getenv(name);
+    return e && e[0] == c;
+}
+
+// Run-time toggle: undecided until its first read, which takes the default from `dflt` (an environment
+// variable); set() wins over the environment whether it comes before or after that read.
+struct Toggle {
+    bool (*dflt)();
+    std::atomic<int> v{-1};
+    bool get() {
+        int x = v.load();
+        if (x < 0) {
+            v.compare_exchange_strong(x, dflt() ? 1 : 0);
+            x = v.load();
+        }
+        return x == 1;
+    }
+    void set(int on) { v.store(on ? 1 : 0); }
+};
 
 }  // namespace dgs

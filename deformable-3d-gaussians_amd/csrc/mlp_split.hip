@@ -2321,10 +2321,7 @@ static const double kDwsShapeCost[5] = {1.0, 0.34, 0.58, 0.30, 0.41};
 // target: workgroups of the plan (256, one per CU; the slab scratch is sized for it; fewer with
 // reserved CUs)
 static WPlan split_wplan(const Flags &F, int target = 256) {
-    static const bool model = [] {  // A/B only: the MFMA-tile cost model
-        const char *e = getenv("DGS_DWS_TILE_MODEL");
-        return e && *e == '1';
-    }();
+    static const bool model = env_starts("DGS_DWS_TILE_MODEL", '1');  // A/B only: the MFMA-tile cost model
     return make_wplan(F, target, 1.5, 4.0, model ? nullptr : kDwsShapeCost);
 }
 
@@ -2372,10 +2369,7 @@ static int reserved_cus() {
 static int mlp_cus() { return std::max(1, cu_count() - reserved_cus()); }
 static Blocks block_split(int N) {
     const int nb = div_up(N, BM);
-    static const bool off = [] {
-        const char *e = getenv("DGS_MLP_NO_TAIL");
-        return e && e[0] == '1';
-    }();
+    static const bool off = env_starts("DGS_MLP_NO_TAIL", '1');
     if (off || nb == 0) return {nb, 0};
     const int ncu = mlp_cus();
     const int rounds = div_up(nb, ncu), last = nb - ncu * (rounds - 1);
@@ -2386,10 +2380,7 @@ static Blocks block_split(int N) {
 // (two launches in flight on two streams must not share one). DGS_MLP_STATIC=1: one launch block per
 // block, no queue (A/B).
 static uint32_t *block_queue(hipStream_t stream, int kernel) {
-    static const bool off = [] {
-        const char *e = getenv("DGS_MLP_STATIC");
-        return e && e[0] == '1';
-    }();
+    static const bool off = env_starts("DGS_MLP_STATIC", '1');
     if (off) return nullptr;
     static std::mutex mu;
     static std::map<std::pair<int, hipStream_t>, uint32_t *> words;
@@ -2435,10 +2426,7 @@ size_t saved_floats(int flags, int N) {
 // value split once), 0 = the fp32-input MFMA k_dw of mlp.hip, both on the same [rows][Ns] arrays (the
 // bf16 k_dw / k_dwg variants, modes 1 and 2, were removed with the bf16x6 arithmetic in round 6)
 static int dw_mode() {
-    static const int m = [] {
-        const char *e = getenv("DGS_MLP_SPLIT_DW");
-        return (e && e[0] == '0') ? 0 : 3;
-    }();
+    static const int m = env_starts("DGS_MLP_SPLIT_DW", '0') ? 0 : 3;
     return m;
 }
 static int dw_split_once(const Flags &F, size_t Ns, const float *dz, const float *saved, float *slabs,
@@ -2497,10 +2485,7 @@ int forward(int flags, int N, const float *xyz, const float *t, const float *pac
     {
         ScopedTimer tm("mlp_fwd", stream);  // k_fwd only: the class's FLOP count is the trunk's + heads'
         const bool fold = P.F.uniform_t;  // t_emb folded into the biases (a.tc is set above)
-        static const bool fwd8 = [] {  // DGS_MLP_FWD8=0: the 16-wave k_fwd (A/B)
-            const char *e = getenv("DGS_MLP_FWD8");
-            return !(e && e[0] == '0');
-        }();
+        static const bool fwd8 = !env_starts("DGS_MLP_FWD8", '0');  // DGS_MLP_FWD8=0: the 16-wave k_fwd (A/B)
         if (saved && fold && fwd8)
             hipLaunchKernelGGL(k_fwd8, dim3(grid), dim3(NTHR8), 0, stream, a);
         else if (saved && fold)
@@ -2579,10 +2564,7 @@ int backward(int flags, int N, const float *packed, const float *saved, const fl
             // the 8-wave k_bwd8 (bitwise equal to the 16-wave kernel): neutral on the bf16x6 split (r5u),
             // +0.5 % steps/s on the f16 split (mlp_bwd 0.333 -> 0.325 ms, profiles/r6f_mlp_variants_ab.txt);
             // DGS_MLP_BWD8=0 keeps the 16-wave k_bwd
-            static const bool bwd8 = [] {
-                const char *e = getenv("DGS_MLP_BWD8");
-                return !(e && e[0] == '0');
-            }();
+            static const bool bwd8 = !env_starts("DGS_MLP_BWD8", '0');
             if (bwd8)
                 hipLaunchKernelGGL(k_bwd8, dim3(grid), dim3(NTHR8), 0, stream, b);
             else

@@ -4,22 +4,33 @@
 // Replaces diff_gaussian_rasterization._C (un-vendored submodule, .gitmodules:4-7) behind the call
 // contract of gaussian_renderer/__init__.py:53-124.
 //
-// Pipeline (one HIP stream, all buffers in HBM, SoA per-Gaussian geometry):
-//   k_preprocess   1 thread / Gaussian: cull, Sigma3D, EWA Sigma2D, conic, radius, tile rect, SH->RGB,
-//                  depth key (float bits; culled -> all-ones)
-//   depth sort     hipcub radix sort of the N Gaussians by depth (stable: ties in index order)
-//   scan           inclusive sum of tiles_touched in depth order -> pair offsets; the pair count
-//                  is copied to pinned host memory behind an event (speculative binning, below)
-//   k_duplicate    emit (tile, id) pairs in depth order into the speculative capacity
-//   radix sort     stable, on the tile bits only (16-bit keys): same final order as upstream's
-//                  sort of (tile << 32 | depth_bits) keys over Gaussian-index-ordered pairs
-//   k_ranges       [start,end) per tile (pair count read on the device)
-//   k_blend_fwd    1 workgroup (4 waves) / 16x16 tile, LDS-staged 256-Gaussian batches, block-wide
-//                  early exit; writes colour, depth, final T, last contributor
-//   k_blend_bwd    back-to-front replay from the block's max contributor; the 12 per-Gaussian
-//                  gradient sums reduce-scattered across the wave (permlane32/16 swaps + DPP) and
-//                  added with 3 four-lane atomics per (wave, Gaussian)
+// Pipeline (one HIP stream, all buffers in HBM, SoA per-Gaussian geometry). The default path:
+//   k_preprocess     1 thread / Gaussian: cull, Sigma3D, EWA Sigma2D, conic, radius, tile rect, SH->RGB,
+//                    depth key (float bits; culled -> all-ones); zeroes the backward's accumulators
+//   k_rect_count     rect binning, Gaussians in index order: per (256-Gaussian block, tile) pair counts
+//   k_rect_colscan   column scan of the count matrix -> tile starts and ranges; stores the pair count into
+//                    a pinned host word the host polls (speculative binning, below: no event, no copy)
+//   k_rect_place     every block writes its Gaussians' ids into its slice of each tile's list
+//   k_tile_sort      per-tile stable sort of the list by depth key (LDS; global scratch for long lists)
+//   k_blend_fwd      1 workgroup (4 waves) / 16x16 tile, LDS-staged 256-Gaussian batches, block-wide
+//                    early exit; writes colour, depth, final T, last contributor
+//   k_blend_bwd2     back-to-front replay from the block's max contributor, two pixels per lane; the 12
+//                    per-Gaussian gradient sums reduced across the wave and added with float atomics
 //   k_preprocess_bwd 1 thread / Gaussian: conic->Sigma2D->(Sigma3D, mean), projection, SH, Sigma3D->(s,q)
+// dgs_render_frames (render_raster_frame) runs the same stages up to the tile lists, forward only, and
+// blends with k_blend_img (+ k_depth8).
+// The other paths, by the environment variable (or dgs_debug_set_* call) that selects them:
+//   DGS_BINNING=sort     sort binning, also taken past rect binning's tile / cell limits: global depth
+//                        order, hipcub inclusive scan of tiles_touched in that order (pair count copied to
+//                        the pinned word behind an event), k_duplicate emits (tile, id) pairs, stable radix
+//                        sort on the tile bits, k_ranges
+//   DGS_TILE_SORT=0      global depth order: radix sort of the Gaussians by depth key (radix.hip), then
+//                        rect binning over that order and no k_tile_sort
+//   DGS_HIPCUB_SORT=1    hipcub radix sorts instead of radix.hip (implies sort binning)
+//   DGS_BLEND1=1         k_blend_bwd: the one-pixel-per-lane blend backward
+//   DGS_BLEND_SEG=1      k_blend_bwd2s: segmented blend backward from checkpoints k_blend_fwd<true> leaves
+//   DGS_BLEND_FWD2=1     k_blend_fwd2: the two-pixels-per-lane forward blend
+//   DGS_DETERMINISTIC=1  k_blend_bwd2<.., true> + k_rect_gather: per-pair slots summed in a fixed order
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -2278,7 +2289,7 @@ struct dgs_raster_ctx {
     const float *means3D = nullptr, *shs = nullptr, *colors = nullptr, *opac = nullptr, *scales = nullptr,
                 *rots = nullptr, *cov = nullptr;
     const float *shs_rest = nullptr;  // split SH rows (dgs_raster_forward_split_sh): shs = features_dc
-    DevBuf geom, bin, img, acc, tmp, rect;
+    DevBuf geom, bin, img, acc, rect;
     // k_rect_colscan's generation-tagged tile totals: a buffer of their own, zeroed whenever it is
     // (re)allocated, so it only ever holds 0 or words a colscan launch wrote (never stale count-matrix
     // data whose upper half could equal the current generation)
@@ -2328,93 +2339,40 @@ size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 // DGS_BLEND1=1: the one-pixel-per-lane blend backward (k_blend_bwd, 4 waves per tile) instead of the
 // packed two-pixel one (k_blend_bwd2, the default)
 bool blend_one_pixel() {
-    static const bool v = [] {
-        const char *e = getenv("DGS_BLEND1");
-        return e && e[0] == '1';
-    }();
+    static const bool v = env_starts("DGS_BLEND1", '1');
     return v;
-}
-
-// DGS_BLEND_SEG=1: segmented blend backward (k_blend_bwd2s: SEG-long segments of every tile's list as
-// independent work items, from checkpoints the forward leaves) instead of k_blend_bwd2's one serial
-// replay per tile
-std::atomic<int> g_blend_seg{-1};  // -1: not decided yet (DGS_BLEND_SEG), else dgs_debug_set_blend_seg
-bool blend_segmented() {
-    int v = g_blend_seg.load();
-    if (v < 0) {
-        const char *e = getenv("DGS_BLEND_SEG");
-        int want = e && e[0] == '1' ? 1 : 0;
-        g_blend_seg.compare_exchange_strong(v, want);
-        v = g_blend_seg.load();
-    }
-    return v == 1;
-}
-
-// DGS_DETERMINISTIC=1 / dgs_raster_set_deterministic(1): the blend backward (rect binning) writes per-pair
-// slots that k_rect_gather sums in a fixed order instead of float atomics into acc: bitwise reproducible
-// gradients at the cost of the slot traffic (96 B per pair written and read)
-std::atomic<int> g_det{-1};
-bool blend_deterministic() {
-    int v = g_det.load();
-    if (v < 0) {
-        const char *e = getenv("DGS_DETERMINISTIC");
-        int want = e && e[0] == '1' ? 1 : 0;
-        g_det.compare_exchange_strong(v, want);
-        v = g_det.load();
-    }
-    return v == 1;
-}
-
-// DGS_BLEND_FWD2=1 / dgs_debug_set_blend_fwd2: the two-pixels-per-lane forward blend (k_blend_fwd2)
-std::atomic<int> g_fwd2{-1};
-bool blend_fwd2() {
-    int v = g_fwd2.load();
-    if (v < 0) {
-        const char *e = getenv("DGS_BLEND_FWD2");
-        int want = e && e[0] == '1' ? 1 : 0;
-        g_fwd2.compare_exchange_strong(v, want);
-        v = g_fwd2.load();
-    }
-    return v == 1;
-}
-
-// DGS_TILE_SORT=0: rect binning over the global depth sort's order (k_rect_* on depth-ordered Gaussians)
-// instead of index order + the per-tile depth sort (k_tile_sort, the default); dgs_debug_set_tile_sort
-std::atomic<int> g_tile_sort{-1};
-bool tile_sort_enabled() {
-    int v = g_tile_sort.load();
-    if (v < 0) {
-        const char *e = getenv("DGS_TILE_SORT");
-        int want = e && e[0] == '0' ? 0 : 1;
-        g_tile_sort.compare_exchange_strong(v, want);
-        v = g_tile_sort.load();
-    }
-    return v == 1;
 }
 
 // DGS_HIPCUB_SORT=1: hipcub::DeviceRadixSort for the depth and tile sorts instead of radix.hip
 bool hipcub_sort() {
-    static const bool v = [] {
-        const char *e = getenv("DGS_HIPCUB_SORT");
-        return e && e[0] == '1';
-    }();
+    static const bool v = env_starts("DGS_HIPCUB_SORT", '1');
     return v;
 }
 
-// Binning mode: 0 = rect binning up to RECT_MAX_TILES tiles and RECT_MAX_CELLS count-matrix cells
-// (the default), 1 = duplicate + tile-key radix sort + ranges for every image. Initialized from
-// DGS_BINNING=sort (or DGS_HIPCUB_SORT=1); dgs_debug_set_binning switches it at run time.
-std::atomic<int> g_binning{-1};
+// DGS_BLEND_SEG=1 / dgs_debug_set_blend_seg: segmented blend backward (k_blend_bwd2s: SEG-long segments of
+// every tile's list as independent work items, from checkpoints the forward leaves) instead of
+// k_blend_bwd2's one serial replay per tile
+Toggle g_blend_seg{[] { return env_starts("DGS_BLEND_SEG", '1'); }};
 
-int binning_mode() {
-    int m = g_binning.load();
-    if (m < 0) {
-        const char *e = getenv("DGS_BINNING");
-        m = ((e && strcmp(e, "sort") == 0) || hipcub_sort()) ? 1 : 0;
-        g_binning.store(m);
-    }
-    return m;
-}
+// DGS_DETERMINISTIC=1 / dgs_raster_set_deterministic(1): the blend backward (rect binning) writes per-pair
+// slots that k_rect_gather sums in a fixed order instead of float atomics into acc: bitwise reproducible
+// gradients at the cost of the slot traffic (96 B per pair written and read)
+Toggle g_det{[] { return env_starts("DGS_DETERMINISTIC", '1'); }};
+
+// DGS_BLEND_FWD2=1 / dgs_debug_set_blend_fwd2: the two-pixels-per-lane forward blend (k_blend_fwd2)
+Toggle g_fwd2{[] { return env_starts("DGS_BLEND_FWD2", '1'); }};
+
+// DGS_TILE_SORT=0 / dgs_debug_set_tile_sort(0): rect binning over the global depth sort's order (k_rect_*
+// on depth-ordered Gaussians) instead of index order + the per-tile depth sort (k_tile_sort, the default)
+Toggle g_tile_sort{[] { return !env_starts("DGS_TILE_SORT", '0'); }};
+
+// DGS_BINNING=sort (or DGS_HIPCUB_SORT=1) / dgs_debug_set_binning(1): duplicate + tile-key radix sort +
+// ranges for every image, instead of rect binning up to RECT_MAX_TILES tiles and RECT_MAX_CELLS
+// count-matrix cells (the default)
+Toggle g_sort_binning{[] {
+    const char *e = getenv("DGS_BINNING");
+    return (e && strcmp(e, "sort") == 0) || hipcub_sort();
+}};
 
 // process-wide launch generations of k_rect_colscan: a tag never repeats across contexts whose
 // buffers may be recycled
@@ -2427,7 +2385,7 @@ uint32_t next_rect_gen() {
 
 bool rect_binning(int gx, int gy, int P) {
     const int T = gx * gy;
-    return binning_mode() == 0 && T <= RECT_MAX_TILES && rect_place_lds(gx, gy, false) <= 65536 &&
+    return !g_sort_binning.get() && T <= RECT_MAX_TILES && rect_place_lds(gx, gy, false) <= 65536 &&
            (long long)div_up(P, 256) * T <= RECT_MAX_CELLS;
 }
 
@@ -2717,7 +2675,7 @@ static int bin_and_blend(dgs_raster_ctx *c, int cap, int P, int device, hipStrea
         c->cfin = cfin;
         todo = (uint32_t *)c->segq.p + 4;
     }
-    if (!ckpt && blend_fwd2()) {
+    if (!ckpt && g_fwd2.get()) {
         ScopedTimer tm("blend_fwd", stream);
         hipLaunchKernelGGL(k_blend_fwd2, dim3(T), dim3(B2), 0, stream, c->ranges, c->vals, (uint32_t)cap, c->W, c->H, c->gx,
                            c->xy, c->conic_o, c->rgbd, c->s.bg, c->final_T, c->n_contrib, out_color, out_depth);
@@ -2770,6 +2728,150 @@ static int resolve_count(dgs_raster_ctx *c, hipStream_t stream) {
     return DGS_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// frame setup: the stages up to the pair count, one copy for the training forward (raster_forward) and
+// dgs_render_frames (render_raster_frame)
+// ------------------------------------------------------------------------------------------------
+// the hipcub scan / depth-sort scratch at the end of the geometry buffer
+struct GeomScratch {
+    char *p = nullptr;
+    size_t scan_bytes = 0, sort_bytes = 0;
+};
+
+// Size and carve c->geom for P Gaussians. The slot after `offsets` holds the forward's clamped flags
+// (P bytes), or with own_radii the radii (4 P bytes) of a caller that has no array of its own for them.
+static int carve_geom(dgs_raster_ctx *c, int P, bool own_radii, hipStream_t stream, GeomScratch *scr) {
+    size_t off_xy = 0, off_co = align_up(off_xy + 8ull * P), off_cd = align_up(off_co + 16ull * P),
+           off_t = align_up(off_cd + 16ull * P), off_o = align_up(off_t + 4ull * P), off_slot = align_up(off_o + 4ull * P);
+    size_t off_dk = align_up(off_slot + (own_radii ? 4ull : 1ull) * P), off_dk2 = align_up(off_dk + 4ull * P),
+           off_gid = align_up(off_dk2 + 4ull * P), off_ord = align_up(off_gid + 4ull * P), off_ts = align_up(off_ord + 4ull * P);
+    if (P > 0) {
+        DGS_HIP_CHECK(scan_tmp_bytes(c->device, P, stream, scr->scan_bytes));
+        DGS_HIP_CHECK(sort_tmp_bytes<uint32_t>(c->device, P, 32, stream, scr->sort_bytes));
+    }
+    const size_t off_st = align_up(off_ts + 4ull * P);
+    if (int rc = c->geom.ensure(off_st + std::max(scr->scan_bytes, scr->sort_bytes) + 256)) return rc;
+    char *g = (char *)c->geom.p;
+    c->xy = (float2 *)(g + off_xy);
+    c->conic_o = (float4 *)(g + off_co);
+    c->rgbd = (float4 *)(g + off_cd);
+    c->tiles = (uint32_t *)(g + off_t);
+    c->offsets = (uint32_t *)(g + off_o);
+    c->clamped = own_radii ? nullptr : (uint8_t *)(g + off_slot);
+    if (own_radii) c->radii = (int *)(g + off_slot);
+    c->dkey = (uint32_t *)(g + off_dk);
+    c->dkey_alt = (uint32_t *)(g + off_dk2);
+    c->gid = (uint32_t *)(g + off_gid);
+    c->order = (uint32_t *)(g + off_ord);
+    c->tiles_sorted = (uint32_t *)(g + off_ts);
+    scr->p = g + off_st;
+    return DGS_OK;
+}
+
+// The frame's binning path (c->rect_mode, c->tsort) and, for rect binning, c->rect carved into the count
+// matrix [blocks][tiles], the tile starts and the pair count, plus the tile totals in c->rtot
+static int carve_rect(dgs_raster_ctx *c, int P, hipStream_t stream) {
+    const int T = c->gx * c->gy;
+    c->rect_mode = P > 0 && rect_binning(c->gx, c->gy, P);
+    c->tsort = c->rect_mode && g_tile_sort.get();
+    if (!c->rect_mode) return DGS_OK;
+    const size_t nb = div_up(P, 256);
+    size_t o_cnt = 0, o_st = align_up(4ull * nb * T), o_n = align_up(o_st + 4ull * T);
+    if (int rc = c->rect.ensure(o_n + 256)) return rc;
+    char *r = (char *)c->rect.p;
+    c->rect_cnt = (uint32_t *)(r + o_cnt);
+    c->rect_start = (uint32_t *)(r + o_st);
+    c->rect_total = (uint32_t *)(r + o_n);
+    const size_t tot_cap = c->rtot.cap;
+    if (int rc = c->rtot.ensure(8ull * T)) return rc;
+    if (c->rtot.cap != tot_cap) DGS_HIP_CHECK(hipMemsetAsync(c->rtot.p, 0, c->rtot.cap, stream));
+    c->rect_tot = (unsigned long long *)c->rtot.p;
+    return DGS_OK;
+}
+
+// Without the per-tile sort: the Gaussians by depth (stable on the index) into c->order, and for sort
+// binning tiles[order[j]] (the scan input) into c->tiles_sorted
+static int depth_order(dgs_raster_ctx *c, int P, GeomScratch &scr, hipStream_t stream, bool dbg) {
+    if (!c->tsort) {
+        ScopedTimer tm("depth_sort", stream);
+        if (hipcub_sort()) {
+            hipcub::DoubleBuffer<uint32_t> kb(c->dkey, c->dkey_alt), vb(c->gid, c->order);
+            DGS_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(scr.p, scr.sort_bytes, kb, vb, P, 0, 32, stream));
+            c->order = vb.Current();  // either buffer, per the pass count
+            hipLaunchKernelGGL(k_gather_tiles, dim3(div_up(P, 256)), dim3(256), 0, stream, P, c->order, c->tiles,
+                               c->tiles_sorted);
+        } else {
+            // the last pass also gathers tiles[order[j]] into tiles_sorted
+            int alt = 0;
+            uint32_t *gid = c->gid, *ord = c->order;
+            if (int rc = radix::sort_pairs<uint32_t>(c->dkey, c->dkey_alt, gid, ord, P, 32, stream, &alt,
+                                                     c->rect_mode ? nullptr : c->tiles,
+                                                     c->rect_mode ? nullptr : c->tiles_sorted))
+                return rc;
+            c->order = alt ? ord : gid;
+        }
+    }
+    DGS_LAUNCH_CHECK("depth_sort", dbg, stream);
+    return DGS_OK;
+}
+
+// The frame's pair count. Rect binning: k_rect_count + k_rect_colscan, which stores it through c->d_total
+// (maxtodo: the segmented backward's word that k_rect_count zeroes, or null). Sort binning: the inclusive
+// scan of tiles_sorted into c->offsets, and with `readback` its last element copied to c->h_total with
+// c->count_ev recorded behind the copy.
+static int count_pairs(dgs_raster_ctx *c, int P, GeomScratch &scr, uint32_t *maxtodo, bool readback,
+                       hipStream_t stream, bool dbg) {
+    if (!c->rect_mode) {
+        DGS_HIP_CHECK(hipcub::DeviceScan::InclusiveSum(scr.p, scr.scan_bytes, c->tiles_sorted, c->offsets, P, stream));
+        if (readback) {
+            DGS_HIP_CHECK(hipMemcpyAsync(c->h_total, c->offsets + (P - 1), 4, hipMemcpyDeviceToHost, stream));
+            DGS_HIP_CHECK(hipEventRecord(c->count_ev, stream));  // wait_count waits on the latest record
+        }
+        return DGS_OK;
+    }
+    const int nb = div_up(P, 256), T = c->gx * c->gy;
+    {
+        ScopedTimer tm("count", stream);
+        hipLaunchKernelGGL(k_rect_count, dim3(nb), dim3(256), 4ull * T, stream, P, c->tsort ? nullptr : c->order, c->xy,
+                           c->radii, c->gx, c->gy, c->rect_cnt, c->rect_total, maxtodo);
+    }
+    DGS_LAUNCH_CHECK("k_rect_count", dbg, stream);
+    {
+        ScopedTimer tm("scan", stream);
+        hipLaunchKernelGGL(k_rect_colscan, dim3(div_up(T, 64)), dim3(1024), 0, stream, nb, T, c->rect_cnt, c->rect_tot,
+                           next_rect_gen(), c->rect_total, c->rect_total + 1, c->rect_start, c->ranges, c->d_total);
+    }
+    DGS_LAUNCH_CHECK("k_rect_colscan", dbg, stream);
+    return DGS_OK;
+}
+
+// Hands a context back: to the pool, its buffers kept for the next forward on the device (an acquirer on
+// another stream is ordered after the stream that last used them, ctx_acquire), or freed when the pool is full
+static void ctx_release(dgs_raster_ctx *c) {
+    c->pending_release = true;
+    std::lock_guard<std::mutex> lk(g_pool_mu);
+    if (g_pool.size() < 64) {
+        g_pool.push_back(c);
+    } else {
+        c->geom.release(); c->bin.release(); c->img.release(); c->acc.release(); c->rect.release();
+        c->rtot.release(); c->ckb.release(); c->segq.release(); c->det.release();
+        if (c->h_total) (void)hipHostFree(c->h_total);
+        delete c;
+    }
+}
+
+// raster_forward's failing returns give the context back (the caller never sees the pointer): whatever
+// the forward enqueued before it failed is on `stream`
+struct CtxGuard {
+    dgs_raster_ctx *c;
+    hipStream_t stream;
+    ~CtxGuard() {
+        if (!c) return;
+        c->last_stream = stream;
+        ctx_release(c);
+    }
+};
+
 static int raster_forward(const dgs_raster_settings *s, int P, int M, const float *means3D, const float *shs,
                           const float *shs_rest, const float *colors_precomp, const float *opacities,
                           const float *scales, const float *rotations, const float *cov3D_precomp, float *out_color,
@@ -2804,6 +2906,8 @@ static int raster_forward(const dgs_raster_settings *s, int P, int M, const floa
     int device = 0;
     DGS_HIP_CHECK(hipGetDevice(&device));
     dgs_raster_ctx *c = ctx_acquire(device, stream);
+    *ctx_out = nullptr;
+    CtxGuard guard{c, stream};  // disarmed where the forward succeeds
     c->s = *s;
     c->P = P;
     c->M = M;
@@ -2819,54 +2923,18 @@ static int raster_forward(const dgs_raster_settings *s, int P, int M, const floa
     const int T = c->gx * c->gy;
     const int HW = c->H * c->W;
     const bool dbg = s->debug != 0;
-    // geometry
-    size_t off_xy = 0, off_co = align_up(off_xy + 8ull * P), off_cd = align_up(off_co + 16ull * P),
-           off_t = align_up(off_cd + 16ull * P), off_o = align_up(off_t + 4ull * P), off_cl = align_up(off_o + 4ull * P);
-    size_t off_dk = align_up(off_cl + P), off_dk2 = align_up(off_dk + 4ull * P), off_gid = align_up(off_dk2 + 4ull * P),
-           off_ord = align_up(off_gid + 4ull * P), off_ts = align_up(off_ord + 4ull * P);
-    size_t scan_tmp = 0, dsort_tmp = 0;
-    if (P > 0) {
-        DGS_HIP_CHECK(scan_tmp_bytes(device, P, stream, scan_tmp));
-        DGS_HIP_CHECK(sort_tmp_bytes<uint32_t>(device, P, 32, stream, dsort_tmp));
-    }
-    size_t off_st = align_up(off_ts + 4ull * P);
-    if (int rc = c->geom.ensure(off_st + std::max(scan_tmp, dsort_tmp) + 256)) { ctx_out[0] = nullptr; delete c; return rc; }
-    char *g = (char *)c->geom.p;
-    c->xy = (float2 *)(g + off_xy);
-    c->conic_o = (float4 *)(g + off_co);
-    c->rgbd = (float4 *)(g + off_cd);
-    c->tiles = (uint32_t *)(g + off_t);
-    c->offsets = (uint32_t *)(g + off_o);
-    c->clamped = (uint8_t *)(g + off_cl);
-    c->dkey = (uint32_t *)(g + off_dk);
-    c->dkey_alt = (uint32_t *)(g + off_dk2);
-    c->gid = (uint32_t *)(g + off_gid);
-    c->order = (uint32_t *)(g + off_ord);
-    c->tiles_sorted = (uint32_t *)(g + off_ts);
+    GeomScratch scr;
+    if (int rc = carve_geom(c, P, false, stream, &scr)) return rc;
     // image state
     size_t off_r = 0, off_T = align_up(off_r + 8ull * T), off_n = align_up(off_T + 4ull * HW);
-    if (int rc = c->img.ensure(off_n + 4ull * HW)) { delete c; return rc; }
+    if (int rc = c->img.ensure(off_n + 4ull * HW)) return rc;
     char *im = (char *)c->img.p;
     c->ranges = (uint2 *)(im + off_r);
     c->final_T = (float *)(im + off_T);
     c->n_contrib = (uint32_t *)(im + off_n);
-    c->rect_mode = P > 0 && rect_binning(c->gx, c->gy, P);
-    if (c->rect_mode) {  // count matrix [blocks][tiles], tile totals, tile starts, pair count
-        const size_t nb = div_up(P, 256);
-        size_t o_cnt = 0, o_st = align_up(4ull * nb * T), o_n = align_up(o_st + 4ull * T);
-        if (int rc = c->rect.ensure(o_n + 256)) return rc;
-        char *r = (char *)c->rect.p;
-        c->rect_cnt = (uint32_t *)(r + o_cnt);
-        c->rect_start = (uint32_t *)(r + o_st);
-        c->rect_total = (uint32_t *)(r + o_n);
-        const size_t tot_cap = c->rtot.cap;
-        if (int rc = c->rtot.ensure(8ull * T)) return rc;
-        if (c->rtot.cap != tot_cap) DGS_HIP_CHECK(hipMemsetAsync(c->rtot.p, 0, c->rtot.cap, stream));
-        c->rect_tot = (unsigned long long *)c->rtot.p;
-    }
-    c->tsort = c->rect_mode && tile_sort_enabled();
-    c->det_fwd = c->rect_mode && blend_deterministic();
-    c->seg_ok = c->rect_mode && blend_segmented();
+    if (int rc = carve_rect(c, P, stream)) return rc;
+    c->det_fwd = c->rect_mode && g_det.get();
+    c->seg_ok = c->rect_mode && g_blend_seg.get();
     if (c->seg_ok) {
         const size_t cap0 = c->segq.cap;
         if (int rc = c->segq.ensure(4ull * (T + 4))) return rc;
@@ -2890,54 +2958,14 @@ static int raster_forward(const dgs_raster_settings *s, int P, int M, const floa
                                out_visible);
         }
         DGS_LAUNCH_CHECK("k_preprocess", dbg, stream);
-        if (!c->tsort) {
-            // Gaussians by depth (stable on the index), then the pair offsets in that order
-            ScopedTimer tm("depth_sort", stream);
-            if (hipcub_sort()) {
-                hipcub::DoubleBuffer<uint32_t> kb(c->dkey, c->dkey_alt), vb(c->gid, c->order);
-                DGS_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(g + off_st, dsort_tmp, kb, vb, P, 0, 32, stream));
-                c->order = vb.Current();  // either buffer, per the pass count
-                hipLaunchKernelGGL(k_gather_tiles, dim3(div_up(P, 256)), dim3(256), 0, stream, P, c->order, c->tiles,
-                                   c->tiles_sorted);
-            } else {
-                // the last pass also gathers tiles[order[j]] (the scan input) into tiles_sorted
-                int alt = 0;
-                uint32_t *gid = c->gid, *ord = c->order;
-                if (int rc = radix::sort_pairs<uint32_t>(c->dkey, c->dkey_alt, gid, ord, P, 32, stream, &alt,
-                                                         c->rect_mode ? nullptr : c->tiles,
-                                                         c->rect_mode ? nullptr : c->tiles_sorted))
-                    return rc;
-                c->order = alt ? ord : gid;
-            }
-        }
-        DGS_LAUNCH_CHECK("depth_sort", dbg, stream);
+        if (int rc = depth_order(c, P, scr, stream, dbg)) return rc;
         if (!c->h_total) {  // coherent + mapped: k_rect_colscan stores the count into it directly
             DGS_HIP_CHECK(hipHostMalloc((void **)&c->h_total, sizeof(uint32_t), hipHostMallocCoherent | hipHostMallocMapped));
             DGS_HIP_CHECK(hipHostGetDevicePointer((void **)&c->d_total, c->h_total, 0));
         }
         if (!c->count_ev) DGS_HIP_CHECK(hipEventCreateWithFlags(&c->count_ev, hipEventDisableTiming));
-        if (c->rect_mode) {
-            const int nb = div_up(P, 256);
-            *(volatile uint32_t *)c->h_total = COUNT_PENDING;  // k_rect_colscan overwrites it
-            {
-                ScopedTimer tm("count", stream);
-                hipLaunchKernelGGL(k_rect_count, dim3(nb), dim3(256), 4ull * T, stream, P, c->tsort ? nullptr : c->order,
-                                   c->xy, c->radii, c->gx,
-                                   c->gy, c->rect_cnt, c->rect_total, c->seg_ok ? (uint32_t *)c->segq.p + 2 : nullptr);
-            }
-            DGS_LAUNCH_CHECK("k_rect_count", dbg, stream);
-            {
-                ScopedTimer tm("scan", stream);
-                hipLaunchKernelGGL(k_rect_colscan, dim3(div_up(T, 64)), dim3(1024), 0, stream, nb, T, c->rect_cnt, c->rect_tot,
-                                   next_rect_gen(), c->rect_total, c->rect_total + 1, c->rect_start, c->ranges,
-                                   c->d_total);
-            }
-            DGS_LAUNCH_CHECK("k_rect_colscan", dbg, stream);
-        } else {
-            DGS_HIP_CHECK(hipcub::DeviceScan::InclusiveSum(g + off_st, scan_tmp, c->tiles_sorted, c->offsets, P, stream));
-            DGS_HIP_CHECK(hipMemcpyAsync(c->h_total, c->offsets + (P - 1), 4, hipMemcpyDeviceToHost, stream));
-        }
-        if (!c->rect_mode) DGS_HIP_CHECK(hipEventRecord(c->count_ev, stream));
+        if (c->rect_mode) *(volatile uint32_t *)c->h_total = COUNT_PENDING;  // k_rect_colscan overwrites it
+        if (int rc = count_pairs(c, P, scr, c->seg_ok ? (uint32_t *)c->segq.p + 2 : nullptr, true, stream, dbg)) return rc;
         int cap = pair_cap_get(device);
         const bool speculative = cap > 0 && !dbg;
         if (!speculative) {
@@ -2949,6 +2977,7 @@ static int raster_forward(const dgs_raster_settings *s, int P, int M, const floa
             c->count_pending = true;
             c->spec_cap = cap;
             c->num_rendered = cap;
+            guard.c = nullptr;
             *ctx_out = c;
             if (num_rendered) *num_rendered = -1;
             return DGS_OK;
@@ -2968,6 +2997,7 @@ static int raster_forward(const dgs_raster_settings *s, int P, int M, const floa
         if (int rc = bin_and_blend(c, 0, P, device, stream, dbg, out_color, out_depth)) return rc;
     }
     c->num_rendered = nr;
+    guard.c = nullptr;
     *ctx_out = c;
     if (num_rendered) *num_rendered = nr;
     return DGS_OK;
@@ -3013,7 +3043,7 @@ static int raster_backward(dgs_raster_ctx *c, const float *dL_dcolor, const floa
     float *acc = (float *)c->acc.p;  // [P][12], zeroed by the forward's k_preprocess
     // deterministic mode: k_rect_gather writes every row of acc (no zeroing needed)
     // deterministic: asked for at this forward too (the tile sort then left the position map)
-    const bool det = blend_deterministic() && c->rect_mode && c->det_fwd && !blend_one_pixel();
+    const bool det = g_det.get() && c->rect_mode && c->det_fwd && !blend_one_pixel();
     // a second backward through the same forward (retain_graph, or a context kept alive): the blend
     // backward adds into the accumulators, so they are cleared first instead of doubling the gradients
     if (c->bwd_done && !det) DGS_HIP_CHECK(hipMemsetAsync(acc, 0, 4ull * ACC_STRIDE * P, stream));
@@ -3130,18 +3160,7 @@ extern "C" int dgs_raster_ctx_num_rendered(dgs_raster_ctx *c) {
 extern "C" void dgs_raster_ctx_free(dgs_raster_ctx *c) {
     if (!c) return;
     (void)resolve_count(c, c->last_stream);  // a deferred count nobody read (forward without backward)
-    // Buffers stay allocated for reuse by the next forward on this device; an acquirer on another
-    // stream is ordered after the stream that last used them (ctx_acquire).
-    c->pending_release = true;
-    std::lock_guard<std::mutex> lk(g_pool_mu);
-    if (g_pool.size() < 64) {
-        g_pool.push_back(c);
-    } else {
-        c->geom.release(); c->bin.release(); c->img.release(); c->acc.release(); c->tmp.release(); c->rect.release();
-        c->rtot.release(); c->ckb.release(); c->segq.release(); c->det.release();
-        if (c->h_total) (void)hipHostFree(c->h_total);
-        delete c;
-    }
+    ctx_release(c);
 }
 
 extern "C" void dgs_raster_set_deferred_count(int on) { g_deferred.store(on ? 1 : 0); }
@@ -3157,16 +3176,16 @@ extern "C" void dgs_debug_set_pair_cap(int device, int cap) {
 
 extern "C" int dgs_debug_pair_cap(int device) { return pair_cap_get(device); }
 
-extern "C" void dgs_debug_set_blend_seg(int on) { g_blend_seg.store(on ? 1 : 0); }
-extern "C" void dgs_raster_set_deterministic(int on) { g_det.store(on ? 1 : 0); }
-extern "C" void dgs_debug_set_tile_sort(int on) { g_tile_sort.store(on ? 1 : 0); }
-extern "C" void dgs_debug_set_blend_fwd2(int on) { g_fwd2.store(on ? 1 : 0); }
-extern "C" int dgs_debug_get_blend_fwd2(void) { return blend_fwd2() ? 1 : 0; }
-extern "C" int dgs_debug_get_tile_sort(void) { return tile_sort_enabled() ? 1 : 0; }
-extern "C" int dgs_raster_get_deterministic(void) { return blend_deterministic() ? 1 : 0; }
-extern "C" int dgs_debug_get_blend_seg(void) { return blend_segmented() ? 1 : 0; }
+extern "C" void dgs_debug_set_blend_seg(int on) { g_blend_seg.set(on); }
+extern "C" void dgs_raster_set_deterministic(int on) { g_det.set(on); }
+extern "C" void dgs_debug_set_tile_sort(int on) { g_tile_sort.set(on); }
+extern "C" void dgs_debug_set_blend_fwd2(int on) { g_fwd2.set(on); }
+extern "C" int dgs_debug_get_blend_fwd2(void) { return g_fwd2.get() ? 1 : 0; }
+extern "C" int dgs_debug_get_tile_sort(void) { return g_tile_sort.get() ? 1 : 0; }
+extern "C" int dgs_raster_get_deterministic(void) { return g_det.get() ? 1 : 0; }
+extern "C" int dgs_debug_get_blend_seg(void) { return g_blend_seg.get() ? 1 : 0; }
 
-extern "C" void dgs_debug_set_binning(int mode) { g_binning.store(mode == 1 ? 1 : 0); }
+extern "C" void dgs_debug_set_binning(int mode) { g_sort_binning.set(mode == 1); }
 
 extern "C" long long dgs_debug_count_wait_ns(long long *waits) {
     if (waits) *waits = g_count_waits.load();
@@ -3205,7 +3224,7 @@ std::mutex g_rws_mu;
 std::map<int, RenderWs *> g_rws;
 }  // namespace
 
-int render_ws_acquire(int F, int P, int H, int W, bool need_depth, hipStream_t stream, RenderWs **out) {
+int render_ws_acquire(int F, int H, int W, bool need_depth, hipStream_t stream, RenderWs **out) {
     int device = 0;
     DGS_HIP_CHECK(hipGetDevice(&device));
     RenderWs *ws = nullptr;
@@ -3269,7 +3288,6 @@ int render_ws_acquire(int F, int P, int H, int W, bool need_depth, hipStream_t s
         set_error("dgs_render_frames: hipEventCreateWithFlags failed");
         return fail(DGS_ERR_HIP);
     }
-    (void)P;
     *out = ws;
     return DGS_OK;
 }
@@ -3305,50 +3323,13 @@ int render_raster_frame(RenderWs *ws, const RenderRasterIn &in, int f, int known
     c->s.bg = in.bg;
     const int T = c->gx * c->gy, HW = c->H * c->W;
     const bool redo = known_count >= 0;
-    // geometry (no clamped bytes), as raster_forward lays it out
-    size_t off_xy = 0, off_co = align_up(off_xy + 8ull * P), off_cd = align_up(off_co + 16ull * P),
-           off_t = align_up(off_cd + 16ull * P), off_o = align_up(off_t + 4ull * P), off_rad = align_up(off_o + 4ull * P);
-    size_t off_dk = align_up(off_rad + 4ull * P), off_dk2 = align_up(off_dk + 4ull * P), off_gid = align_up(off_dk2 + 4ull * P),
-           off_ord = align_up(off_gid + 4ull * P), off_ts = align_up(off_ord + 4ull * P);
-    size_t scan_tmp = 0, dsort_tmp = 0;
-    if (P > 0) {
-        DGS_HIP_CHECK(scan_tmp_bytes(device, P, stream, scan_tmp));
-        DGS_HIP_CHECK(sort_tmp_bytes<uint32_t>(device, P, 32, stream, dsort_tmp));
-    }
-    const size_t off_st = align_up(off_ts + 4ull * P);
-    if (int rc = c->geom.ensure(off_st + std::max(scan_tmp, dsort_tmp) + 256)) return rc;
-    char *g = (char *)c->geom.p;
-    c->xy = (float2 *)(g + off_xy);
-    c->conic_o = (float4 *)(g + off_co);
-    c->rgbd = (float4 *)(g + off_cd);
-    c->tiles = (uint32_t *)(g + off_t);
-    c->offsets = (uint32_t *)(g + off_o);
-    c->radii = (int *)(g + off_rad);
-    c->dkey = (uint32_t *)(g + off_dk);
-    c->dkey_alt = (uint32_t *)(g + off_dk2);
-    c->gid = (uint32_t *)(g + off_gid);
-    c->order = (uint32_t *)(g + off_ord);
-    c->tiles_sorted = (uint32_t *)(g + off_ts);
-    c->clamped = nullptr;
+    GeomScratch scr;
+    if (int rc = carve_geom(c, P, true, stream, &scr)) return rc;  // the radii in place of the clamped bytes
     if (int rc = c->img.ensure(8ull * T)) return rc;  // the tile ranges only
     c->ranges = (uint2 *)c->img.p;
     c->final_T = nullptr;
     c->n_contrib = nullptr;
-    c->rect_mode = P > 0 && rect_binning(c->gx, c->gy, P);
-    if (c->rect_mode) {
-        const size_t nb = div_up(P, 256);
-        size_t o_st = align_up(4ull * nb * T), o_n = align_up(o_st + 4ull * T);
-        if (int rc = c->rect.ensure(o_n + 256)) return rc;
-        char *r = (char *)c->rect.p;
-        c->rect_cnt = (uint32_t *)r;
-        c->rect_start = (uint32_t *)(r + o_st);
-        c->rect_total = (uint32_t *)(r + o_n);
-        const size_t tot_cap = c->rtot.cap;
-        if (int rc = c->rtot.ensure(8ull * T)) return rc;
-        if (c->rtot.cap != tot_cap) DGS_HIP_CHECK(hipMemsetAsync(c->rtot.p, 0, c->rtot.cap, stream));
-        c->rect_tot = (unsigned long long *)c->rtot.p;
-    }
-    c->tsort = c->rect_mode && tile_sort_enabled();
+    if (int rc = carve_rect(c, P, stream)) return rc;
     c->det_fwd = false;
     c->seg_ok = false;
     if (redo && in.depth8) DGS_HIP_CHECK(hipMemsetAsync(ws->dmax + f, 0, 4, stream));
@@ -3365,49 +3346,11 @@ int render_raster_frame(RenderWs *ws, const RenderRasterIn &in, int f, int known
                                (uint8_t *)nullptr);
         }
         DGS_LAUNCH_CHECK("k_preprocess", false, stream);
-        if (!c->tsort) {
-            ScopedTimer tm("depth_sort", stream);
-            if (hipcub_sort()) {
-                hipcub::DoubleBuffer<uint32_t> kb(c->dkey, c->dkey_alt), vb(c->gid, c->order);
-                DGS_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(g + off_st, dsort_tmp, kb, vb, P, 0, 32, stream));
-                c->order = vb.Current();
-                hipLaunchKernelGGL(k_gather_tiles, dim3(div_up(P, 256)), dim3(256), 0, stream, P, c->order, c->tiles,
-                                   c->tiles_sorted);
-            } else {
-                int alt = 0;
-                uint32_t *gid = c->gid, *ord = c->order;
-                if (int rc = radix::sort_pairs<uint32_t>(c->dkey, c->dkey_alt, gid, ord, P, 32, stream, &alt,
-                                                         c->rect_mode ? nullptr : c->tiles,
-                                                         c->rect_mode ? nullptr : c->tiles_sorted))
-                    return rc;
-                c->order = alt ? ord : gid;
-            }
-        }
-        DGS_LAUNCH_CHECK("depth_sort", false, stream);
+        if (int rc = depth_order(c, P, scr, stream, false)) return rc;
         // the frame's pair count: its own host word (a redo already knows it: the device-side dummy word)
         c->h_total = ws->h_counts + f;
         c->d_total = redo ? ws->dummy : ws->d_counts + f;
-        if (c->rect_mode) {
-            const int nb = div_up(P, 256);
-            {
-                ScopedTimer tm("count", stream);
-                hipLaunchKernelGGL(k_rect_count, dim3(nb), dim3(256), 4ull * T, stream, P, c->tsort ? nullptr : c->order,
-                                   c->xy, c->radii, c->gx, c->gy, c->rect_cnt, c->rect_total, (uint32_t *)nullptr);
-            }
-            DGS_LAUNCH_CHECK("k_rect_count", false, stream);
-            {
-                ScopedTimer tm("scan", stream);
-                hipLaunchKernelGGL(k_rect_colscan, dim3(div_up(T, 64)), dim3(1024), 0, stream, nb, T, c->rect_cnt, c->rect_tot,
-                                   next_rect_gen(), c->rect_total, c->rect_total + 1, c->rect_start, c->ranges, c->d_total);
-            }
-            DGS_LAUNCH_CHECK("k_rect_colscan", false, stream);
-        } else {
-            DGS_HIP_CHECK(hipcub::DeviceScan::InclusiveSum(g + off_st, scan_tmp, c->tiles_sorted, c->offsets, P, stream));
-            if (!redo) {
-                DGS_HIP_CHECK(hipMemcpyAsync(c->h_total, c->offsets + (P - 1), 4, hipMemcpyDeviceToHost, stream));
-                DGS_HIP_CHECK(hipEventRecord(c->count_ev, stream));  // wait_count waits on the latest record
-            }
-        }
+        if (int rc = count_pairs(c, P, scr, nullptr, !redo, stream, false)) return rc;
         if (!redo) ws->last = f;
         cap = redo ? known_count : pair_cap_get(device);
         if (!redo && cap <= 0) {  // no learned capacity: this frame waits for its own count, as the forward does

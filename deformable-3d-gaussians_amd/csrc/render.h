@@ -18,9 +18,10 @@ struct RenderRasterIn {
 };
 
 // Takes the device's workspace for one dgs_render_frames call of F frames (held until render_ws_release;
-// calls on one device serialise), sized for P Gaussians and an H x W image; `stream` is ordered after the
-// workspace's previous user. need_depth: depth8 is wanted without a float depth output.
-int render_ws_acquire(int F, int P, int H, int W, bool need_depth, hipStream_t stream, RenderWs **ws);
+// calls on one device serialise), with F count slots and an H x W depth scratch (the per-Gaussian buffers
+// are sized by render_raster_frame); `stream` is ordered after the workspace's previous user. need_depth:
+// depth8 is wanted without a float depth output.
+int render_ws_acquire(int F, int H, int W, bool need_depth, hipStream_t stream, RenderWs **ws);
 void render_ws_release(RenderWs *ws, hipStream_t stream);
 // Enqueues frame f: preprocess, pair count (into the frame's host slot), binning, k_blend_img, k_depth8.
 // known_count < 0: bin for the learned capacity (without one: wait for this frame's count and bin at the

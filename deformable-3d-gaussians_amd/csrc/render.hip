@@ -111,7 +111,7 @@ extern "C" int dgs_render_frames(const dgs_render_frames_args *a, int *redone_fr
     }
     if (a->F == 0) return DGS_OK;
     RenderWs *ws = nullptr;
-    if (int rc = render_ws_acquire(a->F, a->P, a->H, a->W, a->out_depth8 && !a->out_depth, stream, &ws)) return rc;
+    if (int rc = render_ws_acquire(a->F, a->H, a->W, a->out_depth8 && !a->out_depth, stream, &ws)) return rc;
     int rc = DGS_OK, redone = 0;
     for (int f = 0; f < a->F && !rc; f++) rc = frame(a, ws, f, -1, stream);
     // the call's one host wait; after a failure too (result ignored), so that no enqueued frame can still be

@@ -155,6 +155,39 @@ def test_sort_binning_path():
         assert torch.equal(o["color"], color) and torch.equal(o["depth"], depth)
 
 
+@pytest.mark.parametrize("tile_sort", [1, 0])
+@pytest.mark.parametrize("binning", ["rect", "sort"])
+def test_shared_stages_both_callers(binning, tile_sort):
+    """The frame-setup stages the training forward and render_frames share (geometry / rect carve, global depth
+    order, pair count), on the paths the default binning does not reach: sort binning, and rect binning over the
+    global depth order (tile sort off). 300 Gaussians (two 256-thread blocks, the second ragged) on a 48 x 40
+    image (3 x 3 tiles, ragged right and bottom), two (camera, time) frames; both callers run under the same
+    toggles, so the comparison is bitwise."""
+    import os
+    from deformgs import _lib
+    from deformgs.render_frames import render_frames
+    lib = _lib.load()
+    gm, deform = S.gaussians(n=300), S.network()
+    cams = S.cameras(2, width=48, height=40)
+    bg = torch.zeros(3, device="cuda")
+    default = 1 if (os.environ.get("DGS_BINNING") == "sort" or os.environ.get("DGS_HIPCUB_SORT") == "1") else 0
+    ts_before = lib.dgs_debug_get_tile_sort()
+    try:
+        lib.dgs_debug_set_binning(1 if binning == "sort" else 0)
+        lib.dgs_debug_set_tile_sort(tile_sort)
+        ref = [_per_frame(gm, deform, c, bg, False) for c in cams]
+        out = render_frames(cams, gm, deform, bg, outputs=("color", "depth"))
+    finally:
+        lib.dgs_debug_set_binning(default)
+        lib.dgs_debug_set_tile_sort(ts_before)
+    nr = [r[2] for r in ref]
+    print("pair counts: per-frame", nr, "render_frames", out["num_rendered"].tolist(), "redone", out["redone"])
+    assert min(nr) > 0
+    assert out["num_rendered"].tolist() == nr
+    assert torch.equal(out["color"], torch.stack([r[0] for r in ref]))
+    assert torch.equal(out["depth"], torch.stack([r[1] for r in ref]))
+
+
 def test_one_host_wait():
     from deformgs import _lib
     from deformgs.render_frames import render_frames
