@@ -7,6 +7,11 @@ For every <MODEL>/test/ours_* directory: per-view and mean PSNR (loss.psnr) and 
 (dgs_l1_ssim_forward: the reference's 11x11 sigma-1.5 window). LPIPS is recorded as null: the lpips package
 and its VGG weights are not assumed to be present.
 
+--ms_ssim: adds "MS-SSIM" (pytorch_msssim.ms_ssim's definition, data_range 1) and "D-SSIM" = (1 - MS-SSIM) / 2, the
+two further columns of the upstream Deformable-3D-Gaussians metrics.py, to both files: one batched
+deformgs.image_metrics call per group of equally sized images (they must be larger than 160 pixels a side).
+Without the flag both files are what they always were.
+
 --synthetic N: when <MODEL>/test holds no ours_* directory yet, the test set of the synthetic scene is
 rendered first (deformgs.render_cli --mode render), so the script runs with no dataset.
 """
@@ -52,7 +57,22 @@ def read_images(renders_dir, gt_dir, device):
     return renders, gts, names
 
 
-def evaluate(model_paths, ssim_fn=None, device="cuda"):
+def batched_ms_ssim(renders, gts):
+    """MS-SSIM of every (1, 3, H, W) pair: one image_metrics call per image size, one host read."""
+    from .image_metrics import image_metrics
+    groups = {}
+    for i, r in enumerate(renders):
+        groups.setdefault(tuple(r.shape), []).append(i)
+    parts = [(idx, image_metrics([renders[i] for i in idx], [gts[i] for i in idx], ("ms_ssim",))["ms_ssim"])
+             for idx in groups.values()]
+    values = [0.0] * len(renders)
+    for idx, v in parts:
+        for i, x in zip(idx, v.tolist()):
+            values[i] = x
+    return values
+
+
+def evaluate(model_paths, ssim_fn=None, device="cuda", ms_ssim=False):
     """Writes results.json / per_view.json under every model path; -> {model path: results dict}."""
     ssim_fn = ssim_fn or fused_ssim
     full = {}
@@ -76,6 +96,14 @@ def evaluate(model_paths, ssim_fn=None, device="cuda"):
             per_view[method] = {"SSIM": dict(zip(names, torch.tensor(ssims).tolist())),
                                 "PSNR": dict(zip(names, torch.tensor(psnrs).tolist())),
                                 "LPIPS": {n: None for n in names}}
+            if ms_ssim:
+                ms = torch.tensor(batched_ms_ssim(renders, gts))
+                m_ms = ms.mean().item()
+                print("  MS-SSIM: {:>10.7f}".format(m_ms))
+                print("  D-SSIM : {:>10.7f}\n".format((1.0 - m_ms) / 2.0))
+                full[scene_dir][method].update({"MS-SSIM": m_ms, "D-SSIM": (1.0 - m_ms) / 2.0})
+                per_view[method].update({"MS-SSIM": dict(zip(names, ms.tolist())),
+                                         "D-SSIM": dict(zip(names, ((1.0 - ms.double()) / 2.0).tolist()))})
         with open(os.path.join(scene_dir, "results.json"), "w") as fp:
             json.dump(full[scene_dir], fp, indent=True)
         with open(os.path.join(scene_dir, "per_view.json"), "w") as fp:
@@ -83,12 +111,18 @@ def evaluate(model_paths, ssim_fn=None, device="cuda"):
     return full
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(description="PSNR / SSIM of rendered test sets (metrics.py counterpart)")
     ap.add_argument("--model_paths", "-m", required=True, nargs="+")
     ap.add_argument("--synthetic", type=int, default=0, metavar="N")
     ap.add_argument("--res", type=int, nargs=2, default=[800, 800], metavar=("W", "H"))
-    args = ap.parse_args(argv)
+    ap.add_argument("--ms_ssim", action="store_true",
+                    help="also write MS-SSIM and D-SSIM = (1 - MS-SSIM) / 2 (images larger than 160 pixels a side)")
+    return ap
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     if args.synthetic:
         from . import render_cli
         for m in args.model_paths:
@@ -96,7 +130,7 @@ def main(argv=None):
             if not (os.path.isdir(t) and any(d.startswith("ours") for d in os.listdir(t))):
                 render_cli.main(["-m", m, "--synthetic", str(args.synthetic), "--res", str(args.res[0]), str(args.res[1]),
                                  "--mode", "render", "--skip_train"])
-    return evaluate(args.model_paths)
+    return evaluate(args.model_paths, ms_ssim=args.ms_ssim)
 
 
 if __name__ == "__main__":

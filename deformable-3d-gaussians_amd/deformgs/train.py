@@ -56,8 +56,10 @@ def build_viewpoint_stack(cameras, sequence_length):
 
 
 def training_report(iteration, testing_iterations, test_cameras, train_cameras, gaussians, deform, pipe, background,
-                    is_6dof, log=None):
-    """train_baseline.py:210-267 without TensorBoard: test and train-sample L1 / PSNR."""
+                    is_6dof, log=None, ms_ssim=False):
+    """train_baseline.py:210-267 without TensorBoard: test and train-sample L1 / PSNR. ms_ssim: the test
+    entry becomes (L1, PSNR, SSIM, MS-SSIM), the last two from one image_metrics call over the frames
+    rendered here (MS-SSIM None for frames of 160 pixels or less a side)."""
     if iteration not in testing_iterations:
         return None
     out = {}
@@ -75,8 +77,15 @@ def training_report(iteration, testing_iterations, test_cameras, train_cameras, 
                 gts.append(torch.clamp(cam.original_image, 0.0, 1.0))
             images, gts = torch.stack(images), torch.stack(gts)
             out[name] = (float(l1_loss(images, gts)), float(psnr(images, gts).mean()))
+            more = ""
+            if ms_ssim and name == "test":
+                from .image_metrics import MS_SSIM_MIN_SIDE, image_metrics
+                big = min(images.shape[-2:]) > MS_SSIM_MIN_SIDE
+                m = image_metrics(images, gts, ("ssim", "ms_ssim") if big else ("ssim",))
+                out[name] += (float(m["ssim"].mean()), float(m["ms_ssim"].mean()) if big else None)
+                more = f" SSIM {out[name][2]} MS-SSIM {out[name][3]}"
             if log:
-                log(f"[ITER {iteration}] Evaluating {name}: L1 {out[name][0]} PSNR {out[name][1]}")
+                log(f"[ITER {iteration}] Evaluating {name}: L1 {out[name][0]} PSNR {out[name][1]}{more}")
     return out
 
 
@@ -97,7 +106,7 @@ def _glue_step(gaussians, deform, cam, gt, pipe, bg, is_6dof, lambda_dssim, warm
 
 
 def training(dataset, opt, pipe, testing_iterations, saving_iterations, scene, gaussians, deform=None, fused=True,
-             deferred_count=True, seed=0, model_path=None, log=None, on_iteration=None):
+             deferred_count=True, seed=0, model_path=None, log=None, on_iteration=None, report_ms_ssim=False):
     """Runs opt.iterations iterations on `scene` (scene.getTrainCameras() / getTestCameras() /
     cameras_extent, cameras carrying fid and original_image) and the GaussianModel `gaussians`
     (already initialised). Returns a history dict: per-iteration loss, Gaussian count and redo flag,
@@ -168,7 +177,7 @@ def training(dataset, opt, pipe, testing_iterations, saving_iterations, scene, g
                 gaussians.max_radii2D = torch.where(vis, torch.maximum(gaussians.max_radii2D, radii.float()),
                                                     gaussians.max_radii2D)
                 rep = training_report(iteration, testing_iterations, scene.getTestCameras(), scene.getTrainCameras(),
-                                      gaussians, deform, pipe, bg, dataset.is_6dof, log)
+                                      gaussians, deform, pipe, bg, dataset.is_6dof, log, report_ms_ssim)
                 if rep is not None:
                     hist["report"][iteration] = rep
                 if iteration in saving_iterations and model_path and rank == 0:
@@ -335,6 +344,8 @@ def build_parser():
     ap.add_argument("--save_iterations", type=int, nargs="+", default=[])
     ap.add_argument("--test_iterations", type=int, nargs="+", default=[])
     ap.add_argument("--is_6dof", action="store_true")
+    ap.add_argument("--report_ms_ssim", action="store_true",
+                    help="test reports also give the test set's SSIM and MS-SSIM (frames above 160 pixels a side)")
     ap.add_argument("--nerfies_kind", choices=["vrig", "nerf", "interp", "other"], default=None,
                     help="split rule of a Nerfies directory (default: from the name of SOURCE's parent directory)")
     return ap
@@ -387,7 +398,7 @@ def main(argv=None):
         what = f"{args.n} Gaussians init @ {args.res}x{args.res}"
     torch.manual_seed(0)
     hist = training(dataset, opt, PipelineParams(), tests, saves, scene, g, deferred_count=not args.no_deferred,
-                    model_path=args.model_path or None,
+                    model_path=args.model_path or None, report_ms_ssim=args.report_ms_ssim,
                     log=(lambda s: print(s, flush=True)) if rank == 0 else None)
     fb = float(np.median(hist["iter_ms"])) if hist["iter_ms"] else 0.0
     out = {"metric": f"train iters/s (full loop: densify + Adam + reports), {what}",

@@ -260,6 +260,23 @@ int dgs_l1_ssim_backward(int C, int H, int W, const float *img, const float *gt,
  * Gaussian with its outer product's total matched to the reference's fp32 2-D window (ssim.hip). */
 void dgs_l1_ssim_window(float *out11);
 
+/* ---- batched image metrics, forward only (utils/image_utils.py:19-21 psnr, utils/loss_utils.py:41-73 ssim,
+ * pytorch_msssim.ms_ssim(data_range=1) as the upstream Deformable-3D-Gaussians metrics.py calls it) ----
+ * img, gt: (F,C,H,W) in [0,1]. what: a set of DGS_METRIC_*. out (device): (F, 3 + 2*5*C) = per frame
+ * [PSNR, SSIM, MS-SSIM, cs[5][C], ssim[5][C]]: the per-level, per-channel means of the MS-SSIM pyramid
+ * (valid 11x11 sigma-1.5 filter; avg_pool2d(2, 2, padding = side mod 2) between levels);
+ * MS-SSIM = mean_c prod_{l<4} relu(cs[l][c])^w[l] * relu(ssim[4][c])^w[4]. Unrequested slots are NaN.
+ * PSNR of identical images is +inf. A fixed number of launches for any F, no host wait, no atomics:
+ * results are bitwise reproducible and a frame's result does not depend on the batch around it.
+ * scratch: dgs_image_metrics_scratch_bytes bytes (0 for arguments dgs_image_metrics rejects).
+ * DGS_ERR_ARGS: null pointer, non-positive size, empty or unknown `what`, MS-SSIM with min(H,W) <= 160. */
+#define DGS_METRIC_PSNR 1u
+#define DGS_METRIC_SSIM 2u
+#define DGS_METRIC_MS_SSIM 4u
+size_t dgs_image_metrics_scratch_bytes(int F, int C, int H, int W, unsigned what);
+int dgs_image_metrics(int F, int C, int H, int W, const float *img, const float *gt, unsigned what, float *out,
+                      void *scratch, void *stream);
+
 /* ---- simple-knn replacement: mean squared distance to the 3 nearest neighbours ---- */
 int dgs_knn_dist2(int P, const float *points, float *dist2, void *stream);
 
