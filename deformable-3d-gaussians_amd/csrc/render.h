@@ -1,5 +1,5 @@
-// The rasterizer side of dgs_render_frames (render.hip), implemented in raster.hip next to the kernels
-// and the binning it shares with the training forward.
+// The rasterizer side of dgs_render_frames (render.hip), implemented in raster.hip next to the binning
+// driver it shares with the training forward (the kernels: raster_preprocess.h, raster_bin.h, raster_blend.h).
 #pragma once
 #include "dgs_common.h"
 

@@ -2,8 +2,9 @@
 //
 // The counterpart of render_baseline.py's render loops (render_set and the interpolate_* variants,
 // render_baseline.py:57-66 per frame: deform.step(xyz, fid) -> render()): per frame the deformation
-// network's inference forward, the render-input glue and the forward-only rasterizer (raster.hip:
-// k_preprocess<., true>, the training forward's binning, k_blend_img, k_depth8), all enqueued on one
+// network's inference forward, the render-input glue and the forward-only rasterizer (raster.hip's
+// render_raster_frame: raster_preprocess.h k_preprocess<., true>, the training forward's binning,
+// raster_blend.h k_blend_img and k_depth8), all enqueued on one
 // stream without a host wait in between.
 //
 // Host waits per call: one, for the last frame's pair count at the end (render_wait_counts), plus one

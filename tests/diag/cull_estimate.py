@@ -2,7 +2,7 @@
 
 The reference bins every Gaussian into each tile of its 3-sigma square (getRect); the blend kernels
 skip, at staging, the pairs whose alpha >= 1/255 ellipse misses every pixel centre of the tile
-(raster.hip tile_reach). This counts, on the bench scene (synth-100k @ 800x800, camera 0, fid 0.5,
+(raster_blend.h tile_reach). This counts, on the bench scene (synth-100k @ 800x800, camera 0, fid 0.5,
 normalized rotations), the pairs that (a) the exact ellipse-vs-tile test and (b) the ellipse's
 axis-aligned bounding box would keep. (b) is the only variant that keeps k_rect_place's rank trick
 (ranks are popcounts over per-row x per-column lane masks, i.e. rectangles).

@@ -1,4 +1,4 @@
-"""The blend kernels' tile culling (raster.hip `tile_reach`) is conservative: a Gaussian it drops from
+"""The blend kernels' tile culling (raster_blend.h `tile_reach`) is conservative: a Gaussian it drops from
 a tile's staged batch has alpha < 1/255 at every pixel centre of the tile, i.e. every pixel would
 have skipped it anyway (images and gradients unchanged). Checked on the CPU with a float32 numpy
 restatement of the bound against brute-force alphas, on the oracle's own preprocess geometry."""
@@ -11,7 +11,7 @@ from oracle.raster import OracleRaster, make_settings
 
 
 def tile_reach(gx, gy, cx, cy, cz, o, x0, y0):
-    """float32 restatement of raster.hip tile_reach (bound widened by 1 % + 1e-3)."""
+    """float32 restatement of raster_blend.h tile_reach (bound widened by 1 % + 1e-3)."""
     f = np.float32
     if not (o >= f(1.0 / 255.0)):
         return False

@@ -1,4 +1,4 @@
-"""CPU address audit of the deterministic blend backward (raster.hip): the index
+"""CPU address audit of the deterministic blend backward (raster_blend.h, raster_bin.h): the index
 expressions of k_tile_sort<true> (the position map `pre`), k_blend_bwd2<DEPTH, true> (per-pair slot
 writes: zeros past the replayed prefix, zeros for tile-culled entries, the reduced sums of the replayed
 ones) and k_rect_gather (the per-Gaussian slot reads of rect_walk), replayed on real tile lists, against
