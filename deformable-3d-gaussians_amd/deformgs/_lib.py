@@ -41,6 +41,12 @@ class RowJob(ctypes.Structure):
     _fields_ = [("src", P), ("dst", P), ("width", I)]
 
 
+class JpegInfo(ctypes.Structure):
+    """dgs_jpeg_info (include/dgs.h)."""
+    _fields_ = [("width", ctypes.c_int32), ("height", ctypes.c_int32), ("hs", ctypes.c_int32), ("vs", ctypes.c_int32),
+                ("blocks_w", ctypes.c_int32 * 3), ("blocks_h", ctypes.c_int32 * 3), ("qt", (ctypes.c_uint16 * 64) * 3)]
+
+
 class Frame(ctypes.Structure):
     """dgs_frame (include/dgs.h)."""
     _fields_ = [("viewmatrix", P), ("projmatrix", P), ("campos", P), ("tanfovx", F), ("tanfovy", F)]
@@ -130,6 +136,11 @@ _SIGS = {
     "dgs_ingest_unfilter": ([I, I, I, I, P, P, P, P], I),
     "dgs_ingest_resample": ([ctypes.c_int64, I, I, I, P, P, P, I, P, P], I),
     "dgs_ingest_to_float": ([I, I, I, P, P, P], I),
+    # JPEG: (bytes, len, info*, err, err_len) / (bytes, len, info*, out, capacity, err, err_len): host, thread-safe;
+    # (B, W, H, hs, vs, coef, qtables, rgb8_out, scratch, stream): device
+    "dgs_jpeg_header": ([ctypes.c_char_p, SZ, ctypes.POINTER(JpegInfo), ctypes.c_char_p, SZ], I),
+    "dgs_jpeg_coefficients": ([ctypes.c_char_p, SZ, ctypes.POINTER(JpegInfo), P, SZ, ctypes.c_char_p, SZ], I),
+    "dgs_ingest_jpeg": ([I, I, I, I, I, P, P, P, P, P], I),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -8,6 +8,7 @@ class ModelParams:
         self.white_background = False
         self.is_blender = True
         self.is_6dof = False
+        self.images = "images"  # -i / --images: the image directory of a Colmap SOURCE
         self.D, self.W, self.multires = 8, 256, 10
         self.__dict__.update(kw)
 

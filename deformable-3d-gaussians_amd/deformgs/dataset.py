@@ -1,5 +1,6 @@
-"""Dataset directories: the counterpart of scene.Scene with the D-NeRF (Blender-style) reader
-readNerfSyntheticInfo and the Nerfies-format reader readNerfiesInfo (NeRF-DS, HyperNeRF vrig / interp / misc).
+"""Dataset directories: the counterpart of scene.Scene with the Colmap reader readColmapSceneInfo (a monocular
+capture through convert.py), the D-NeRF (Blender-style) reader readNerfSyntheticInfo and the Nerfies-format
+reader readNerfiesInfo (NeRF-DS, HyperNeRF vrig / interp / misc).
 
 Mirrors (file:line in the reference):
   scene/dataset_readers.py:223-266  readCamerasFromTransforms: R / T from transform_matrix, fid = frame["time"],
@@ -13,6 +14,12 @@ Mirrors (file:line in the reference):
   scene/dataset_readers.py:476-509  readNerfiesInfo: the first train_num cameras train and the rest test with
                                     eval; points3d.ply or points.npy as (xyz - center) * scale
   utils/camera_utils.py:92-112      camera_nerfies_from_JSON: focal_length * ratio, the old `tangential` key
+  scene/colmap_loader.py            the binary and text readers of sparse/0/{cameras,images,points3D}, qvec2rotmat
+  scene/dataset_readers.py:101-141  readColmapCameras: R = qvec2rotmat(q)^T, T = tvec, the fields of view from the
+                                    focal length(s) of a SIMPLE_PINHOLE / PINHOLE camera, the image looked up by
+                                    base name, fid = int(image_name) / (number of images - 1)
+  scene/dataset_readers.py:172-220  readColmapSceneInfo: cameras sorted by name as strings, every 8th the test
+                                    set with eval; points3D.ply, else points3D.bin / .txt converted
   scene/dataset_readers.py:77-98    getNerfppNorm: translate = -mean camera centre, radius = 1.1 x largest
                                     distance from it
   utils/camera_utils.py:21-44       loadCam's resolution rule (target_resolution)
@@ -22,18 +29,20 @@ Mirrors (file:line in the reference):
 
 The images go through deformgs/ingest.py (HIP unfilter + composite + resize on a GPU device), one batch per
 camera set; every camera's original_image is a view into that batch. The Nerfies reader needs only what the
-reference's needs: JSON, points.npy and 8-bit RGB PNGs, whose size comes from the file header (png_size).
+reference's needs: JSON, points.npy and 8-bit RGB PNGs, whose size comes from the file header (png_size). A
+Colmap directory's images are baseline JPEG (or RGB PNG) files: deformgs/ingest.py decodes both.
 
-Deviation: the reference writes a generated point cloud into the dataset directory (points3d.ply). Here SOURCE
-is read only; the cloud is written as MODEL/input.ply, where the reference copies it anyway, and a later run
-builds the same cloud again (the colours from a seeded generator).
+Deviation: the reference writes a generated or converted point cloud into the dataset directory (points3d.ply,
+sparse/0/points3D.ply). Here SOURCE is read only; the cloud is written as MODEL/input.ply, where the reference
+copies it anyway, and a later run builds the same cloud again (the colours from a seeded generator).
 
-Out of scope: the DTU reader (it needs cv2 / imageio behaviour), the Colmap and plenoptic readers (their images
-are JPEG) and the Dynamic-360 one; gt_alpha_mask and load2gpu_on_the_fly. Scene names such a directory in its
-ValueError.
+Out of scope: the DTU reader (it needs cv2 / imageio behaviour), the plenoptic and Dynamic-360 readers;
+gt_alpha_mask (an RGBA image in a Colmap directory is refused) and load2gpu_on_the_fly. Scene names such a
+directory in its ValueError.
 """
 import json
 import os
+import struct
 from argparse import Namespace
 from collections import namedtuple
 
@@ -59,6 +68,21 @@ def png_size(path):
     if len(head) < 24 or head[:8] != b"\x89PNG\r\n\x1a\n" or head[12:16] != b"IHDR":
         raise ValueError(f"{path}: not a PNG file")
     return int.from_bytes(head[16:20], "big"), int.from_bytes(head[20:24], "big")
+
+
+def jpeg_size(path):
+    """(width, height) from the frame header of a JPEG file (markers only, no decode)."""
+    from .jpeg import jpeg_size as size
+    return size(path)
+
+
+def image_size(path):
+    """(width, height) of a PNG or JPEG file, told apart by the signature; header only."""
+    with open(path, "rb") as f:
+        head = f.read(8)
+    if head[:2] == b"\xff\xd8":
+        return jpeg_size(path)
+    return png_size(path)
 
 
 def read_cameras_from_transforms(path, transformsfile, extension=".png"):
@@ -282,6 +306,211 @@ def read_nerfies(path, eval, model_path=None, nerfies_kind=None, seed=0):
     return SceneInfo(point_cloud=pcd, train_cameras=train, test_cameras=test, nerf_normalization=norm, ply_path=ply_path)
 
 
+COLMAP_MODELS = {0: ("SIMPLE_PINHOLE", 3), 1: ("PINHOLE", 4), 2: ("SIMPLE_RADIAL", 4), 3: ("RADIAL", 5), 4: ("OPENCV", 8),
+                 5: ("OPENCV_FISHEYE", 8), 6: ("FULL_OPENCV", 12), 7: ("FOV", 5), 8: ("SIMPLE_RADIAL_FISHEYE", 4),
+                 9: ("RADIAL_FISHEYE", 5), 10: ("THIN_PRISM_FISHEYE", 12)}
+ColmapCamera = namedtuple("ColmapCamera", "id model width height params")
+ColmapImage = namedtuple("ColmapImage", "id qvec tvec camera_id name")
+
+
+def qvec2rotmat(qvec):
+    """Rotation matrix of a unit quaternion (w, x, y, z): colmap_loader.py:43-53, each entry with its operations
+    in the reference's order (the golden comparison is bitwise)."""
+    w, x, y, z = qvec[0], qvec[1], qvec[2], qvec[3]
+    return np.array([[1 - 2 * y ** 2 - 2 * z ** 2, 2 * x * y - 2 * w * z, 2 * z * x + 2 * w * y],
+                     [2 * x * y + 2 * w * z, 1 - 2 * x ** 2 - 2 * z ** 2, 2 * y * z - 2 * w * x],
+                     [2 * z * x - 2 * w * y, 2 * y * z + 2 * w * x, 1 - 2 * x ** 2 - 2 * y ** 2]])
+
+
+class _Records:
+    """Little-endian records of a Colmap .bin file; a short file is a ValueError."""
+
+    def __init__(self, path):
+        self.path = path
+        with open(path, "rb") as f:
+            self.data = f.read()
+        self.pos = 0
+
+    def take(self, fmt):
+        size = struct.calcsize("<" + fmt)
+        if self.pos + size > len(self.data):
+            raise ValueError(f"{self.path}: truncated Colmap file")
+        out = struct.unpack_from("<" + fmt, self.data, self.pos)
+        self.pos += size
+        return out
+
+    def skip(self, size):
+        if size < 0 or self.pos + size > len(self.data):
+            raise ValueError(f"{self.path}: truncated Colmap file")
+        self.pos += size
+
+    def cstring(self):
+        end = self.data.find(b"\0", self.pos)
+        if end < 0:
+            raise ValueError(f"{self.path}: truncated Colmap file")
+        out = self.data[self.pos:end].decode("utf-8")
+        self.pos = end + 1
+        return out
+
+
+def _data_lines(path):
+    with open(path) as f:
+        return [ln.strip() for ln in f]
+
+
+def read_colmap_intrinsics(path):
+    """colmap_loader.py:209-235 (cameras.bin) / :149-171 (cameras.txt) -> {camera_id: ColmapCamera}."""
+    cams = {}
+    if path.endswith(".bin"):
+        rec = _Records(path)
+        for _ in range(rec.take("Q")[0]):
+            cid, mid, w, h = rec.take("iiQQ")
+            if mid not in COLMAP_MODELS:
+                raise ValueError(f"{path}: unknown Colmap camera model id {mid}")
+            name, n = COLMAP_MODELS[mid]
+            cams[cid] = ColmapCamera(cid, name, w, h, np.array(rec.take("d" * n)))
+        return cams
+    for ln in _data_lines(path):
+        if ln and ln[0] != "#":
+            el = ln.split()
+            cams[int(el[0])] = ColmapCamera(int(el[0]), el[1], int(el[2]), int(el[3]), np.array(tuple(map(float, el[4:]))))
+    return cams
+
+
+def read_colmap_extrinsics(path):
+    """colmap_loader.py:174-206 (images.bin) / :238-264 (images.txt) -> {image_id: ColmapImage} in file order;
+    the per-image 2D points (24 bytes each, or the second line of a text record) are skipped."""
+    images = {}
+    if path.endswith(".bin"):
+        rec = _Records(path)
+        for _ in range(rec.take("Q")[0]):
+            v = rec.take("idddddddi")
+            name = rec.cstring()
+            rec.skip(24 * rec.take("Q")[0])
+            images[v[0]] = ColmapImage(v[0], np.array(v[1:5]), np.array(v[5:8]), v[8], name)
+        return images
+    lines = _data_lines(path)
+    k = 0
+    while k < len(lines):
+        ln = lines[k]
+        k += 1
+        if ln and ln[0] != "#":
+            el = ln.split()
+            if len(el) < 10:
+                raise ValueError(f"{path}: an image line needs 10 fields, got {len(el)}")
+            images[int(el[0])] = ColmapImage(int(el[0]), np.array(tuple(map(float, el[1:5]))),
+                                             np.array(tuple(map(float, el[5:8]))), int(el[8]), el[9])
+            k += 1  # the line of 2D points (it may be empty)
+    return images
+
+
+def read_colmap_points(path):
+    """colmap_loader.py:118-146 (points3D.bin) / :87-115 (points3D.txt) -> xyz (n, 3), rgb (n, 3) float64."""
+    if path.endswith(".bin"):
+        rec = _Records(path)
+        n = rec.take("Q")[0]
+        if 43 * n > len(rec.data):
+            raise ValueError(f"{path}: truncated Colmap file")
+        xyz, rgb = np.empty((n, 3)), np.empty((n, 3))
+        for i in range(n):
+            v = rec.take("QdddBBBd")
+            xyz[i], rgb[i] = v[1:4], v[4:7]
+            rec.skip(8 * rec.take("Q")[0])
+        return xyz, rgb
+    xyz, rgb = [], []
+    for ln in _data_lines(path):
+        if ln and ln[0] != "#":
+            el = ln.split()
+            xyz.append(tuple(map(float, el[1:4])))
+            rgb.append(tuple(map(int, el[4:7])))
+    return np.array(xyz, np.float64).reshape(-1, 3), np.array(rgb, np.float64).reshape(-1, 3)
+
+
+def colmap_model_files(path):
+    """(images file, cameras file) of sparse/0: the .bin pair, else the .txt pair, else None."""
+    for ext in (".bin", ".txt"):
+        pair = [os.path.join(path, "sparse", "0", n + ext) for n in ("images", "cameras")]
+        if all(os.path.isfile(p) for p in pair):
+            return pair
+    return None
+
+
+def read_colmap_cameras(path, images=None):
+    """dataset_readers.py:101-141 without the image load, in the order of the images file. images: the
+    directory of the image files under SOURCE (default "images")."""
+    pair = colmap_model_files(path)
+    if pair is None:
+        raise ValueError(f"{path}: a Colmap dataset without sparse/0/{{images,cameras}}.{{bin,txt}}: that layout is unsupported")
+    extrinsics, intrinsics = read_colmap_extrinsics(pair[0]), read_colmap_intrinsics(pair[1])
+    folder = os.path.join(path, "images" if images is None else images)
+    num_frames = len(extrinsics)
+    if num_frames < 2:
+        raise ValueError(f"{path}: a Colmap model of {num_frames} image(s): the frame time is int(name) / (images - 1), "
+                         "which needs at least two")
+    infos = []
+    for extr in extrinsics.values():
+        if extr.camera_id not in intrinsics:
+            raise ValueError(f"{pair[0]}: image {extr.name} refers to camera {extr.camera_id}, which {pair[1]} does not hold")
+        intr = intrinsics[extr.camera_id]
+        R = np.transpose(qvec2rotmat(extr.qvec))
+        T = np.array(extr.tvec)
+        if intr.model == "SIMPLE_PINHOLE":
+            fovy, fovx = focal2fov(intr.params[0], intr.height), focal2fov(intr.params[0], intr.width)
+        elif intr.model == "PINHOLE":
+            fovy, fovx = focal2fov(intr.params[1], intr.height), focal2fov(intr.params[0], intr.width)
+        else:
+            raise ValueError(f"{pair[1]}: camera model {intr.model}: Colmap camera model not handled: only undistorted "
+                             "datasets (PINHOLE or SIMPLE_PINHOLE cameras) supported!")
+        image_path = os.path.join(folder, os.path.basename(extr.name))
+        image_name = os.path.basename(image_path).split(".")[0]
+        try:
+            number = int(image_name)
+        except ValueError:
+            raise ValueError(f"{pair[0]}: image name {extr.name!r}: a Colmap image must be named by its frame number "
+                             "(the frame time is int(name) / (images - 1))") from None
+        with open(image_path, "rb") as f:
+            head = f.read(26)
+        if head[:8] == b"\x89PNG\r\n\x1a\n" and len(head) == 26 and head[25] in (4, 6):
+            raise ValueError(f"{image_path}: an image with an alpha channel in a Colmap directory (gt_alpha_mask) is unsupported")
+        infos.append(CameraInfo(uid=intr.id, R=R, T=T, FovY=fovy, FovX=fovx, image_path=image_path, image_name=image_name,
+                                width=intr.width, height=intr.height, fid=number / (num_frames - 1)))
+    return infos
+
+
+def read_colmap(path, eval, images=None, model_path=None, llffhold=8):
+    """dataset_readers.py:172-220. The point cloud is sparse/0/points3D.ply if present; otherwise points3D.bin,
+    else points3D.txt, written to MODEL/input.ply when model_path is given (the reference writes
+    sparse/0/points3D.ply; SOURCE is never written here) and read back from there."""
+    cams = sorted(read_colmap_cameras(path, images), key=lambda c: c.image_name)  # as strings: "10" < "2"
+    if eval:
+        train = [c for i, c in enumerate(cams) if i % llffhold != 0]
+        test = [c for i, c in enumerate(cams) if i % llffhold == 0]
+    else:
+        train, test = cams, []
+    norm = nerfpp_norm(train)
+    sparse = os.path.join(path, "sparse", "0")
+    ply_path = os.path.join(sparse, "points3D.ply")
+    if os.path.exists(ply_path):
+        pcd = fetch_ply(ply_path)
+    else:
+        for name in ("points3D.bin", "points3D.txt"):
+            if os.path.isfile(os.path.join(sparse, name)):
+                xyz, rgb = read_colmap_points(os.path.join(sparse, name))
+                break
+        else:
+            raise ValueError(f"{path}: no sparse/0/points3D.ply, .bin or .txt (a Colmap dataset brings its point cloud)")
+        ply_path = None
+        if model_path:
+            os.makedirs(model_path, exist_ok=True)
+            ply_path = os.path.join(model_path, "input.ply")
+            store_ply(ply_path, xyz, rgb)
+            pcd = fetch_ply(ply_path)
+        else:
+            pcd = BasicPointCloud(points=xyz.astype(np.float32), colors=rgb.astype(np.uint8) / 255.0,
+                                  normals=np.zeros((xyz.shape[0], 3), np.float32))
+    return SceneInfo(point_cloud=pcd, train_cameras=train, test_cameras=test, nerf_normalization=norm, ply_path=ply_path)
+
+
 # scene/__init__.py:45-63 in its order: marker file or directory -> the format it announces
 _FORMAT_MARKERS = (("sparse", "Colmap"), ("transforms_train.json", "D-NeRF"), ("cameras_sphere.npz", "DTU"),
                    ("dataset.json", "Nerfies"), ("poses_bounds.npy", "plenoptic video (Neu3D)"),
@@ -289,22 +518,32 @@ _FORMAT_MARKERS = (("sparse", "Colmap"), ("transforms_train.json", "D-NeRF"), ("
 
 
 def dataset_format(source_path):
-    """"D-NeRF" or "Nerfies" by the reference's dispatch order; ValueError for the formats it also knows but
-    this package does not read, and for a directory it would not recognise either."""
+    """"Colmap", "D-NeRF" or "Nerfies" by the reference's dispatch order; ValueError for the formats it also
+    knows but this package does not read, for a sparse/ without a readable sparse/0 model, and for a directory
+    it would not recognise either."""
     for marker, name in _FORMAT_MARKERS:
         if os.path.exists(os.path.join(source_path, marker)):
             if name in ("D-NeRF", "Nerfies"):
                 return name
+            if name == "Colmap":
+                if colmap_model_files(source_path) is not None:
+                    return name
+                raise ValueError(f"{source_path}: found {marker}, a Colmap dataset without "
+                                 "sparse/0/{images,cameras}.{bin,txt}: that layout is unsupported")
             raise ValueError(f"{source_path}: found {marker}, a {name} dataset: that format is unsupported "
                              "(D-NeRF and Nerfies directories are read)")
     raise ValueError(f"{source_path}: could not recognise the scene type (no transforms_train.json of a D-NeRF "
                      "directory and no dataset.json of a Nerfies one)")
 
 
-def read_scene_info(source_path, white_background, eval, init_points=100_000, model_path=None, nerfies_kind=None):
+def read_scene_info(source_path, white_background, eval, init_points=100_000, model_path=None, nerfies_kind=None,
+                    images=None):
     """The reader of the directory's format (dataset_format). init_points only applies to D-NeRF directories:
-    a Nerfies one starts from its own point cloud."""
-    if dataset_format(source_path) == "Nerfies":
+    a Nerfies or a Colmap one starts from its own point cloud. images: the image directory of a Colmap one."""
+    fmt = dataset_format(source_path)
+    if fmt == "Colmap":
+        return read_colmap(source_path, eval, images=images, model_path=model_path)
+    if fmt == "Nerfies":
         return read_nerfies(source_path, eval, model_path=model_path, nerfies_kind=nerfies_kind)
     return read_nerf_synthetic(source_path, white_background, eval, init_points=init_points, model_path=model_path)
 
@@ -352,10 +591,11 @@ def load_cameras(cam_infos, resolution, white_background, device):
 
 
 class Scene:
-    """scene/__init__.py:23-112 for a D-NeRF or a Nerfies directory (dataset_format). args: source_path,
+    """scene/__init__.py:23-112 for a Colmap, a D-NeRF or a Nerfies directory (dataset_format). args: source_path,
     model_path, white_background, eval, resolution (default -1), init_points (default 100 000; D-NeRF only),
-    nerfies_kind (default None: the directory-name rule), data_device (default "cuda"). white_background has
-    no effect on RGB images (Nerfies captures carry no alpha)."""
+    nerfies_kind (default None: the directory-name rule), images (default "images": the image directory of a
+    Colmap SOURCE), data_device (default "cuda"). white_background has no effect on images without alpha
+    (Nerfies and Colmap captures)."""
 
     def __init__(self, args, gaussians, load_iteration=None):
         from .deform_model import searchForMaxIteration
@@ -371,7 +611,8 @@ class Scene:
         info = read_scene_info(args.source_path, args.white_background, args.eval,
                                init_points=getattr(args, "init_points", 100_000),
                                model_path=None if self.loaded_iter else self.model_path,
-                               nerfies_kind=getattr(args, "nerfies_kind", None))
+                               nerfies_kind=getattr(args, "nerfies_kind", None),
+                               images=getattr(args, "images", None))
         if not self.loaded_iter:
             dest = os.path.join(self.model_path, "input.ply")
             if info.ply_path != dest:  # SOURCE/points3d.ply: copied, as upstream

@@ -1,4 +1,5 @@
-"""Dataset image ingest: PNG files -> the float (N, 3, h, w) images the cameras hold (Camera.original_image).
+"""Dataset image ingest: PNG and baseline JPEG files -> the float (N, 3, h, w) images the cameras hold
+(Camera.original_image).
 
 What the reference does per image with PIL and numpy (scene/dataset_readers.py:242-255, utils/camera_utils.py:44,
 utils/general_utils.py:23-29), restated in integer arithmetic so that it is bit-exact without PIL:
@@ -15,13 +16,23 @@ On a GPU device the host only parses chunks and inflates (zlib releases the GIL:
 the filtered scanlines of all images of one (W, H, channels) go up in one copy and steps 1-4 are HIP kernels
 (csrc/ingest.hip) on the current stream. On the CPU the same steps run in numpy: the oracle of the GPU tests
 and the path for CPU-only use (a CPU device asked for explicitly, never a silent fallback).
+
+A JPEG file (recognised by its signature, not its name) replaces steps 1-2 by libjpeg-turbo's default decode,
+which is what the reference gets from Image.open: the host parses markers and Huffman-decodes to quantised
+coefficients (csrc/jpeg_decode.h through ctypes, which releases the GIL: the same pool of threads, writing into
+one host buffer per group), the coefficients and the per-image quantisation tables go up in one copy each, and
+dequantisation, the 8x8 inverse DCT, chroma upsampling and YCbCr -> RGB are HIP kernels (csrc/jpeg.hip); steps
+3-4 follow unchanged. On the CPU deformgs/jpeg.py does all of it in Python and numpy. There is no alpha, so
+white_background has no effect. Images are grouped by (format, W, H, channels or chroma sampling).
 """
+import ctypes
 import math
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
 
+from . import jpeg
 from .png import inflate_png, unfilter
 
 MAX_INFLATE_THREADS = 16
@@ -136,6 +147,95 @@ def inflate_all(items, threads=MAX_INFLATE_THREADS):
         return list(pool.map(one, items))
 
 
+PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+
+
+def image_format(data):
+    """"png" or "jpeg" from the first bytes of the file."""
+    if data[:8] == PNG_SIGNATURE:
+        return "png"
+    if data[:2] == b"\xff\xd8":
+        return "jpeg"
+    raise ValueError("ingest_images takes PNG or JPEG files (neither signature found)")
+
+
+def _pool_map(fn, items, threads):
+    n = max(1, min(int(threads), MAX_INFLATE_THREADS, len(items)))
+    if n == 1:
+        return [fn(it) for it in items]
+    with ThreadPoolExecutor(max_workers=n) as pool:
+        return list(pool.map(fn, items))
+
+
+def front_end_all(items, native_jpeg, threads=MAX_INFLATE_THREADS):
+    """-> [(format, W, H, channels or (hs, vs), payload)] in input order. PNG: payload = the validated filtered
+    scanlines (inflate_all). JPEG: only the header is read here; payload = (file bytes, header), the header
+    being a _lib.JpegInfo (native_jpeg: the C++ front end) or a jpeg.JpegHeader (the Python one)."""
+    def one(item):
+        data = _read(item)
+        if image_format(data) == "png":
+            w, h, ch, raw = inflate_png(data)
+            if ch not in (3, 4):
+                raise ValueError(f"ingest_images takes RGB or RGBA images, got {ch} channel(s)")
+            validate_scanlines(raw, w, h, ch)
+            return "png", w, h, ch, raw
+        hd = jpeg_header_native(data) if native_jpeg else jpeg.parse_header(data)
+        return "jpeg", hd.width, hd.height, (hd.hs, hd.vs), (data, hd)
+    return _pool_map(one, items, threads)
+
+
+def jpeg_header_native(data):
+    """dgs_jpeg_header (csrc/jpeg_decode.h) -> _lib.JpegInfo; ValueError with the front end's reason."""
+    from . import _lib
+    info = _lib.JpegInfo()
+    err = ctypes.create_string_buffer(256)
+    if _lib.load().dgs_jpeg_header(data, len(data), ctypes.byref(info), err, len(err)) != 0:
+        raise ValueError(err.value.decode(errors="replace"))
+    return info
+
+
+def jpeg_blocks(info):
+    """8x8 blocks of the three components together (padded to whole MCUs)."""
+    return sum(int(info.blocks_w[c]) * int(info.blocks_h[c]) for c in range(3))
+
+
+def jpeg_coefficients_native(data, info=None, out=None):
+    """dgs_jpeg_coefficients -> int16 (blocks, 64), natural order, component-major (into `out` when given)."""
+    from . import _lib
+    info = info or jpeg_header_native(data)
+    if out is None:
+        out = np.empty((jpeg_blocks(info), 64), np.int16)
+    err = ctypes.create_string_buffer(256)
+    if _lib.load().dgs_jpeg_coefficients(data, len(data), ctypes.byref(info), out.ctypes.data_as(ctypes.c_void_p),
+                                         out.size, err, len(err)) != 0:
+        raise ValueError(err.value.decode(errors="replace"))
+    return out
+
+
+def jpeg_decode_host(files, threads=MAX_INFLATE_THREADS):
+    """files: [(bytes, _lib.JpegInfo)] of one (W, H, sampling) -> int16 (B, blocks, 64) coefficients in one host
+    buffer, filled by at most 16 threads, and the uint16 (B, 3, 64) quantisation tables."""
+    n = jpeg_blocks(files[0][1])
+    coef = np.empty((len(files), n, 64), np.int16)
+    qt = np.stack([np.ctypeslib.as_array(info.qt).reshape(3, 64) for _, info in files]).astype(np.uint16)
+    _pool_map(lambda k: jpeg_coefficients_native(files[k][0], files[k][1], coef[k]), list(range(len(files))), threads)
+    return coef, qt
+
+
+def jpeg_device(coef, qt, W, H, hs, vs, device):
+    """Host coefficients (B, blocks, 64) and tables (B, 3, 64) -> device uint8 (B, H, W, 3): one upload each,
+    then dgs_ingest_jpeg on the current stream."""
+    from . import _lib
+    B, n = coef.shape[0], coef.shape[1]
+    cd = torch.from_numpy(coef).to(device)
+    qd = torch.from_numpy(qt.view(np.int16)).to(device)  # torch has no uint16 arithmetic; the bits are what goes up
+    scratch = torch.empty(B * n * 64, dtype=torch.uint8, device=device)
+    rgb8 = torch.empty((B, H, W, 3), dtype=torch.uint8, device=device)
+    _lib.check(_lib.load().dgs_ingest_jpeg(B, W, H, hs, vs, _lib.ptr(cd), _lib.ptr(qd), _lib.ptr(rgb8), _lib.ptr(scratch),
+                                           _lib.stream_ptr(rgb8.device)), "ingest_jpeg")
+    return rgb8
+
+
 def unfilter_device(scan, B, W, H, channels, lut=None):
     """scan: device uint8 tensor of B x H x (1 + W*channels) validated scanlines -> (B, H, W, channels) bytes,
     or (B, H, W, 3) composited with the device table `lut` (channels 4 only)."""
@@ -202,6 +302,30 @@ def ingest_group_device(raws, W, H, channels, white_background, size, device, ou
     return out, rgb8
 
 
+def ingest_jpeg_group_device(files, W, H, sampling, size, device, out=None, threads=MAX_INFLATE_THREADS):
+    """One (W, H, sampling) group of JPEG files [(bytes, _lib.JpegInfo)] on the device: threaded Huffman
+    decode into one host buffer, two uploads, IDCT + upsampling + colour, then resize -> float as for PNG.
+    -> (float (B, 3, h, w), uint8 (B, h, w, 3))."""
+    w, h = size
+    coef, qt = jpeg_decode_host(files, threads)
+    rgb8 = jpeg_device(coef, qt, W, H, sampling[0], sampling[1], device)
+    if w != W:
+        rgb8 = _resample_device(rgb8, 2, w)
+    if h != H:
+        rgb8 = _resample_device(rgb8, 1, h)
+    if out is None:
+        out = torch.empty((len(files), 3, h, w), dtype=torch.float32, device=device)
+    _to_float_device(rgb8, out)
+    return out, rgb8
+
+
+def ingest_jpeg_group_numpy(files, size):
+    """The same in Python and numpy (deformgs/jpeg.py). files: [(bytes, jpeg.JpegHeader)]."""
+    px = np.stack([jpeg.upsample_color(jpeg.idct_planes(jpeg.decode_coefficients(d, hd), hd), hd) for d, hd in files])
+    rgb8 = np.ascontiguousarray(resize_numpy(px, size))
+    return np.ascontiguousarray(rgb8.transpose(0, 3, 1, 2)).astype(np.float32) / np.float32(255.0), rgb8
+
+
 def ingest_group_numpy(raws, W, H, channels, white_background, size):
     """The same steps in numpy. -> (float32 (B, 3, h, w), uint8 (B, h, w, 3)) arrays."""
     px = np.stack([unfilter(r, W, H, channels) for r in raws])
@@ -210,17 +334,19 @@ def ingest_group_numpy(raws, W, H, channels, white_background, size):
 
 
 def ingest_images(images, white_background, size=None, device="cuda", return_uint8=False, threads=MAX_INFLATE_THREADS):
-    """images: PNG files as bytes or paths (8-bit RGB or RGBA). size: None (keep), (w, h), or a function
-    (W, H) -> (w, h) of the file's size (the -r rule). -> float32 (N, 3, h, w) on `device`, in input order
-    (with return_uint8 also the uint8 (N, h, w, 3) image). Images are grouped by (W, H, channels), one launch
-    sequence per group; all groups must reach one target size. Raises ValueError on malformed files."""
+    """images: PNG (8-bit RGB or RGBA) or baseline JPEG files as bytes or paths, told apart by their signature.
+    size: None (keep), (w, h), or a function (W, H) -> (w, h) of the file's size (the -r rule). -> float32
+    (N, 3, h, w) on `device`, in input order (with return_uint8 also the uint8 (N, h, w, 3) image). Images are
+    grouped by (format, W, H, channels or chroma sampling), one launch sequence per group; all groups must reach
+    one target size. white_background has no effect on images without alpha (RGB PNG, JPEG). Raises ValueError
+    on malformed or unsupported files."""
     dev = torch.device(device)
     images = list(images)
-    metas = inflate_all(images, threads)
+    metas = front_end_all(images, dev.type == "cuda", threads)
     groups = {}
-    for i, (W, H, ch, _) in enumerate(metas):
-        groups.setdefault((W, H, ch), []).append(i)
-    targets = {_target(size, W, H) for (W, H, _) in groups}
+    for i, (fmt, W, H, kind, _) in enumerate(metas):
+        groups.setdefault((fmt, W, H, kind), []).append(i)
+    targets = {_target(size, W, H) for (_, W, H, _) in groups}
     if len(targets) > 1:
         raise ValueError(f"ingest_images: the images reach different sizes {sorted(targets)}; pass size=(w, h)")
     if not images:
@@ -230,20 +356,24 @@ def ingest_images(images, white_background, size=None, device="cuda", return_uin
     out = torch.empty((len(images), 3, h, w), dtype=torch.float32, device=dev)
     out8 = torch.empty((len(images), h, w, 3), dtype=torch.uint8, device=dev) if return_uint8 else None
     lut = None
-    for (W, H, ch), idx in groups.items():
-        raws = [metas[i][3] for i in idx]
+    for (fmt, W, H, ch), idx in groups.items():
+        raws = [metas[i][4] for i in idx]
         whole = len(groups) == 1  # then the group's result is the output itself
         if dev.type == "cuda":
-            if ch == 4 and lut is None:
-                lut = torch.from_numpy(composite_table(white_background).reshape(-1).copy()).to(dev)
-            f, u = ingest_group_device(raws, W, H, ch, white_background, (w, h), dev, out if whole else None, lut)
+            if fmt == "jpeg":
+                f, u = ingest_jpeg_group_device(raws, W, H, ch, (w, h), dev, out if whole else None, threads)
+            else:
+                if ch == 4 and lut is None:
+                    lut = torch.from_numpy(composite_table(white_background).reshape(-1).copy()).to(dev)
+                f, u = ingest_group_device(raws, W, H, ch, white_background, (w, h), dev, out if whole else None, lut)
         else:
-            f, u = ingest_group_numpy(raws, W, H, ch, white_background, (w, h))
+            if fmt == "jpeg":
+                f, u = ingest_jpeg_group_numpy(raws, (w, h))
+            else:
+                f, u = ingest_group_numpy(raws, W, H, ch, white_background, (w, h))
             f, u = torch.from_numpy(f), torch.from_numpy(u)
         if not (whole and dev.type == "cuda"):
             out[idx] = f.to(dev)
         if out8 is not None:
             out8[idx] = u.to(dev)
     return (out, out8) if return_uint8 else out
-
-

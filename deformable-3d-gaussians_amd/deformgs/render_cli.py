@@ -17,7 +17,8 @@ over the chosen background and resized to --res by deformgs/ingest.py), and gt/ 
 -s SOURCE at a Nerfies directory (dataset.json: NeRF-DS / HyperNeRF) takes both sets from the training reader
 (deformgs/dataset.read_nerfies_cameras: train ids, then val ids as the test set): cameras, frame times and
 ground-truth images from the files; without --res the frame size is the dataset's own after -r, the training
-size.
+size. -s SOURCE at a Colmap directory (sparse/0) does the same through deformgs/dataset.read_colmap: cameras
+sorted by name, every 8th the test set, images from -i / --images (default images).
 """
 import argparse
 import json
@@ -93,6 +94,23 @@ def read_nerfies_sets(source, res, resolution, device, nerfies_kind=None):
     return _Set(*sets)
 
 
+def read_colmap_sets(source, res, resolution, device, images=None):
+    """A Colmap directory -> _Set of Cameras with their ground truth, split as the training reader splits it with
+    --eval (every 8th camera by name is the test set). res as for read_nerfies_sets."""
+    from .dataset import load_cameras, read_colmap
+    info = read_colmap(source, True, images=images)
+    sets = []
+    for part in (info.train_cameras, info.test_cameras):
+        if res is None:
+            sets.append(load_cameras(part, resolution, False, device))
+            continue
+        cams = [Camera(c.R, c.T, FoVx=c.FovX, FoVy=c.FovY, width=res[0], height=res[1], fid=c.fid, uid=k,
+                       data_device=device) for k, c in enumerate(part)]
+        attach_images(cams, [c.image_path for c in part], False, res[0], res[1], device)
+        sets.append(cams)
+    return _Set(*sets)
+
+
 def _iteration(model_path, iteration):
     from .deform_model import searchForMaxIteration
     if iteration >= 0:
@@ -122,6 +140,10 @@ def load_scene(args, device="cuda"):
                     head.weight.mul_(0.01)
                     head.bias.mul_(0.01)
             d0.save_weights(args.model_path, 0)
+    elif args.source_path and os.path.exists(os.path.join(args.source_path, "sparse")):
+        from .dataset import dataset_format
+        dataset_format(args.source_path)  # raises on a sparse/ without a readable sparse/0 model
+        cams = read_colmap_sets(args.source_path, args.res, args.resolution, dev, args.images)
     elif args.source_path and os.path.exists(os.path.join(args.source_path, "dataset.json")) and not os.path.exists(
             os.path.join(args.source_path, "transforms_train.json")):
         cams = read_nerfies_sets(args.source_path, args.res, args.resolution, dev, args.nerfies_kind)
@@ -187,8 +209,9 @@ def build_parser():
     ap.add_argument("--skip_test", action="store_true")
     ap.add_argument("--synthetic", type=int, default=0, metavar="N")
     ap.add_argument("--res", type=int, nargs=2, default=None, metavar=("W", "H"),
-                    help="frame size (default 800 800; for a Nerfies SOURCE the dataset's own size after -r)")
-    ap.add_argument("--resolution", "-r", type=int, default=-1, help="the training script's -r (Nerfies SOURCE)")
+                    help="frame size (default 800 800; for a Nerfies or Colmap SOURCE the dataset's own size after -r)")
+    ap.add_argument("--resolution", "-r", type=int, default=-1, help="the training script's -r (Nerfies or Colmap SOURCE)")
+    ap.add_argument("--images", "-i", default="images", help="image directory of a Colmap SOURCE (under SOURCE)")
     ap.add_argument("--nerfies_kind", choices=["vrig", "nerf", "interp", "other"], default=None)
     ap.add_argument("--frames", type=int, default=None, help="frames of an interpolation mode (default: the reference's)")
     ap.add_argument("--view_index", type=int, default=-1, help="the fixed view of time / view / all / pose (-1: random)")

@@ -348,6 +348,7 @@ def build_parser():
                     help="test reports also give the test set's SSIM and MS-SSIM (frames above 160 pixels a side)")
     ap.add_argument("--nerfies_kind", choices=["vrig", "nerf", "interp", "other"], default=None,
                     help="split rule of a Nerfies directory (default: from the name of SOURCE's parent directory)")
+    ap.add_argument("--images", "-i", default="images", help="image directory of a Colmap SOURCE (under SOURCE)")
     return ap
 
 
@@ -355,7 +356,7 @@ def main(argv=None):
     """Training run with the reference's defaults; prints one JSON line: iters/s over the whole loop
     (densification, reports and Adam included), the reference's fwd+bwd span per iteration, the final
     Gaussian count and the test PSNR. Without -s: the synthetic scene (config 3: a full train loop). With
-    -s SOURCE -m MODEL: a D-NeRF or Nerfies (NeRF-DS / HyperNeRF) dataset directory through
+    -s SOURCE -m MODEL: a Colmap, D-NeRF or Nerfies (NeRF-DS / HyperNeRF) dataset directory through
     deformgs/dataset.Scene; the model is saved at --save_iterations and at the last iteration. The network is
     the user's choice for either format (--non-blender, as --is_blender upstream)."""
     import json
@@ -376,13 +377,15 @@ def main(argv=None):
         if not args.model_path:
             raise SystemExit("train: -s SOURCE needs -m MODEL (where input.ply, cameras.json and the model are written)")
         from .dataset import Scene, dataset_format
-        if dataset_format(args.source_path) == "Nerfies" and not args.non_blender and rank == 0:
-            print(f"warning: {args.source_path} is a Nerfies directory trained with the blender network; "
+        fmt = dataset_format(args.source_path)
+        if fmt in ("Nerfies", "Colmap") and not args.non_blender and rank == 0:
+            print(f"warning: {args.source_path} is a {fmt} directory trained with the blender network; "
                   "real-world captures are meant for --non-blender", flush=True)
         dataset = ModelParams(is_blender=not args.non_blender, is_6dof=args.six_dof or args.is_6dof,
                               white_background=args.white_background, source_path=args.source_path,
                               model_path=args.model_path, eval=args.eval, resolution=args.resolution,
-                              init_points=args.init_points, nerfies_kind=args.nerfies_kind, data_device=str(dev))
+                              init_points=args.init_points, nerfies_kind=args.nerfies_kind, images=args.images,
+                              data_device=str(dev))
         g = GaussianModel(dataset.sh_degree)
         scene = Scene(dataset, g)
         tests = sorted(set(args.test_iterations)) or tests

@@ -458,6 +458,34 @@ int dgs_ingest_resample(int64_t outer, int n_in, int n_out, int inner, const uin
                         const int *coef, int ksize, uint8_t *out, void *stream);
 int dgs_ingest_to_float(int B, int H, int W, const uint8_t *rgb8, float *out, void *stream);
 
+/* ---- baseline JPEG ingest (what PIL's Image.open gives with libjpeg-turbo, bit for bit) ----
+ * The host does the serial part, per file and thread-safe (no global state: the message goes into the
+ * caller's buffer `err` of `err_len` bytes, not to dgs_last_error); both return 0, or -1 with the reason.
+ * dgs_jpeg_header: markers up to the scan header -> info (host). Read: SOF0 / SOF1, 8 bits, three YCbCr
+ * components in one interleaved scan, chroma 1x1 with luma 1x1, 2x1 or 2x2; everything else is refused.
+ * dgs_jpeg_coefficients: Huffman-decodes the scan into out (host, `capacity` int16 values, at least
+ * 64 * sum(blocks_w * blocks_h)): component-major, block-row-major, 64 values per 8x8 block in natural
+ * (de-zigzagged) order, still quantised. info must be the file's own header. Truncated or corrupt entropy
+ * data (a missing EOI, a bad code, a coefficient index past 63, data that does not match the dimensions) is
+ * an error.
+ * dgs_ingest_jpeg (device): B images of one (W, H, hs, vs). coef: B x the buffer above; qtables: (B, 3, 64)
+ * uint16, per image and component; scratch: B * 64 * sum(blocks_w * blocks_h) bytes (the three sample planes
+ * at block-padded size); rgb8_out: (B, H, W, 3) bytes. Dequantise + jidctint.c's 8x8 inverse DCT, jdsample.c's
+ * fancy chroma upsampling, jdcolor.c's YCbCr -> RGB, all in integers. coef and qtables 16-byte aligned, scratch
+ * 8-byte aligned. Two launches on `stream`, no host synchronisation. */
+typedef struct dgs_jpeg_info {
+    int32_t width, height;
+    int32_t hs, vs;          /* luma sampling factors: 1x1 (4:4:4), 2x1 (4:2:2) or 2x2 (4:2:0) */
+    int32_t blocks_w[3];     /* 8x8 blocks per component, padded to whole MCUs */
+    int32_t blocks_h[3];
+    uint16_t qt[3][64];      /* quantisation table per component, natural order */
+} dgs_jpeg_info;
+int dgs_jpeg_header(const uint8_t *bytes, size_t len, dgs_jpeg_info *info, char *err, size_t err_len);
+int dgs_jpeg_coefficients(const uint8_t *bytes, size_t len, const dgs_jpeg_info *info, int16_t *out, size_t capacity,
+                          char *err, size_t err_len);
+int dgs_ingest_jpeg(int B, int W, int H, int hs, int vs, const int16_t *coef, const uint16_t *qtables,
+                    uint8_t *rgb8_out, uint8_t *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
