@@ -141,6 +141,10 @@ _SIGS = {
     "dgs_jpeg_header": ([ctypes.c_char_p, SZ, ctypes.POINTER(JpegInfo), ctypes.c_char_p, SZ], I),
     "dgs_jpeg_coefficients": ([ctypes.c_char_p, SZ, ctypes.POINTER(JpegInfo), P, SZ, ctypes.c_char_p, SZ], I),
     "dgs_ingest_jpeg": ([I, I, I, I, I, P, P, P, P, P], I),
+    # PNG output: (F, H, W, C) / (F, H, W, C, in, out, out_offsets, out_lengths, scratch, stream): deformgs/png_gpu.py
+    "dgs_png_encode_scratch_bytes": ([I, I, I, I], SZ),
+    "dgs_png_out_capacity": ([I, I, I, I], SZ),
+    "dgs_png_encode": ([I, I, I, I, P, P, P, P, P, P], I),
 }
 
 EXPORTED = tuple(_SIGS)

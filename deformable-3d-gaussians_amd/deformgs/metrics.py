@@ -118,6 +118,7 @@ def build_parser():
     ap.add_argument("--res", type=int, nargs=2, default=[800, 800], metavar=("W", "H"))
     ap.add_argument("--ms_ssim", action="store_true",
                     help="also write MS-SSIM and D-SSIM = (1 - MS-SSIM) / 2 (images larger than 160 pixels a side)")
+    ap.add_argument("--png", choices=["zlib", "gpu"], default="zlib", help="--synthetic: the PNG writer of the render step")
     return ap
 
 
@@ -129,7 +130,7 @@ def main(argv=None):
             t = os.path.join(m, "test")
             if not (os.path.isdir(t) and any(d.startswith("ours") for d in os.listdir(t))):
                 render_cli.main(["-m", m, "--synthetic", str(args.synthetic), "--res", str(args.res[0]), str(args.res[1]),
-                                 "--mode", "render", "--skip_train"])
+                                 "--mode", "render", "--skip_train", "--png", args.png])
     return evaluate(args.model_paths, ms_ssim=args.ms_ssim)
 
 

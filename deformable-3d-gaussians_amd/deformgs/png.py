@@ -106,6 +106,31 @@ def unfilter(raw, w, h, bpp):
     return o[1:, 1:].astype(np.uint8)
 
 
+def filter_rows(img):
+    """uint8 (H, W, 3) or (H, W) -> the filtered scanlines (H rows of one filter byte + W * channels bytes) with
+    libpng's adaptive choice: per row the type (None, Sub, Up, Average, Paeth) whose residuals, read as signed
+    bytes, have the least sum of absolute values, ties toward the lower type. Row 0 over a zero previous row,
+    pixel 0 with zero left and upper-left neighbours, as unfilter assumes. Every output byte reads original pixels
+    only: the numpy restatement of k_png_filter (csrc/png_encode.hip)."""
+    a = np.ascontiguousarray(np.asarray(img))
+    if a.dtype != np.uint8 or not (a.ndim == 2 or (a.ndim == 3 and a.shape[2] == 3)) or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError(f"filter_rows takes a uint8 (H, W, 3) or (H, W) array, got {a.dtype} {a.shape}")
+    h, w = a.shape[:2]
+    x = a.reshape(h, w, -1).astype(np.int32)
+    left, up, ul = np.zeros_like(x), np.zeros_like(x), np.zeros_like(x)
+    left[:, 1:] = x[:, :-1]
+    up[1:] = x[:-1]
+    ul[1:, 1:] = x[:-1, :-1]
+    p = left + up - ul
+    pa, pb, pc = np.abs(p - left), np.abs(p - up), np.abs(p - ul)
+    paeth = np.where((pa <= pb) & (pa <= pc), left, np.where(pb <= pc, up, ul))
+    res = np.stack([(x - q).reshape(h, -1) & 255 for q in (np.zeros_like(x), left, up, (left + up) >> 1, paeth)])
+    cost = np.where(res < 128, res, 256 - res).sum(axis=2)
+    types = np.argmin(cost, axis=0)  # the first of equal minima: the lower type
+    rows = res[types, np.arange(h)].astype(np.uint8)
+    return np.concatenate([types.astype(np.uint8)[:, None], rows], axis=1).tobytes()
+
+
 def decode_png(data):
     """-> uint8 array (H, W, 3) RGB, (H, W) grey, (H, W, 4) RGBA or (H, W, 2) grey + alpha. 8 bits per
     channel, the five filter types, no interlace."""

@@ -4,7 +4,8 @@ render_baseline.py:299-350 on render_frames.
 Loads MODEL/point_cloud/iteration_k/point_cloud.ply and MODEL/deform/iteration_k/deform.pth, builds the
 mode's frame list (deformgs/camera_paths.py), renders it with render_frames (8-bit colour and depth straight
 from the blend kernel) and writes <MODEL>/<train|test>/<mode dir>_<k>/renders/%05d.png, depth/%05d.png and,
-for mode render, gt/%05d.png — the reference's directory names — with the stdlib PNG writer. Prints the
+for mode render, gt/%05d.png — the reference's directory names — with the stdlib PNG writer (--png zlib, the
+default) or the device encoder of deformgs/png_gpu.py (--png gpu: the same pixels, smaller files). Prints the
 reference's FPS line for every set (frames / elapsed of the render_frames call between two device
 synchronisations). No video is written (MP4 encoding is out of scope).
 
@@ -171,10 +172,32 @@ def frame_cameras(mode, views, view_index=0, frames=None):
     return cams, [t for _, _, t in fl]
 
 
+def _write_gpu(out, cams, dirs, chunk):
+    """--png gpu: renders, depth and the 8-bit ground truth go through deformgs.png_gpu in chunks of frames; only
+    compressed bytes reach the host."""
+    from .png_gpu import write_frames
+    from .render_frames import default_chunk
+    rgb, dep = out["rgb8"], out["depth8"]
+    n = int(chunk) if chunk else default_chunk(rgb.shape[1], rgb.shape[2], ("rgb8", "depth8"))
+    for k in range(0, len(cams), n):
+        idx = range(k, min(k + n, len(cams)))
+        write_frames([os.path.join(dirs["renders"], f"{i:05d}.png") for i in idx], rgb[k:k + n])
+        write_frames([os.path.join(dirs["depth"], f"{i:05d}.png") for i in idx], dep[k:k + n])
+        if "gt" in dirs:
+            have = [i for i in idx if getattr(cams[i], "original_image", None) is not None]
+            if have:
+                gt = torch.stack([cams[i].original_image[0:3] for i in have])
+                gt8 = (255 * gt.clamp(0, 1)).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+                write_frames([os.path.join(dirs["gt"], f"{i:05d}.png") for i in have], gt8)
+
+
 def render_set(model_path, name, iteration, mode, views, gaussians, deform, background, is_6dof, view_index=0,
-               frames=None, chunk=None):
-    """Renders one camera set for `mode`, writes the PNGs, prints the FPS line. -> the output directory."""
+               frames=None, chunk=None, png="zlib"):
+    """Renders one camera set for `mode`, writes the PNGs, prints the FPS line. -> the output directory.
+    png: "zlib" writes with deformgs.png.write_png from host copies of the frames, "gpu" with deformgs.png_gpu."""
     from .render_frames import render_frames
+    if png not in ("zlib", "gpu"):
+        raise ValueError(f"render_set: png must be 'zlib' or 'gpu', got {png!r}")
     base = os.path.join(model_path, name, f"{DIR_NAMES[mode]}_{iteration}")
     dirs = {k: os.path.join(base, k) for k in (("renders", "depth", "gt") if mode == "render" else ("renders", "depth"))}
     for d in dirs.values():
@@ -186,14 +209,18 @@ def render_set(model_path, name, iteration, mode, views, gaussians, deform, back
                         chunk=chunk)
     torch.cuda.synchronize()
     dt = time.time() - t0
-    rgb, dep = out["rgb8"].cpu().numpy(), out["depth8"].cpu().numpy()
-    for i in range(len(cams)):
-        write_png(os.path.join(dirs["renders"], f"{i:05d}.png"), rgb[i])
-        write_png(os.path.join(dirs["depth"], f"{i:05d}.png"), dep[i])
-        if mode == "render" and getattr(cams[i], "original_image", None) is not None:
-            gt = cams[i].original_image[0:3]
-            gt8 = (255 * gt.clamp(0, 1)).to(torch.uint8).permute(1, 2, 0).contiguous().cpu().numpy()
-            write_png(os.path.join(dirs["gt"], f"{i:05d}.png"), gt8)
+    if png == "gpu":
+        if cams:
+            _write_gpu(out, cams, dirs, chunk)
+    else:
+        rgb, dep = out["rgb8"].cpu().numpy(), out["depth8"].cpu().numpy()
+        for i in range(len(cams)):
+            write_png(os.path.join(dirs["renders"], f"{i:05d}.png"), rgb[i])
+            write_png(os.path.join(dirs["depth"], f"{i:05d}.png"), dep[i])
+            if mode == "render" and getattr(cams[i], "original_image", None) is not None:
+                gt = cams[i].original_image[0:3]
+                gt8 = (255 * gt.clamp(0, 1)).to(torch.uint8).permute(1, 2, 0).contiguous().cpu().numpy()
+                write_png(os.path.join(dirs["gt"], f"{i:05d}.png"), gt8)
     fps = len(cams) / dt if dt > 0 and cams else 0.0
     print(f"Test FPS: \033[1;35m{fps:.5f}\033[0m, Num. of GS: {gaussians.get_xyz.shape[0]}", flush=True)
     return base
@@ -220,6 +247,9 @@ def build_parser():
     ap.add_argument("--is_6dof", action="store_true")
     ap.add_argument("--non_blender", action="store_true")
     ap.add_argument("--chunk", type=int, default=None)
+    ap.add_argument("--png", choices=["zlib", "gpu"], default="zlib",
+                    help="the PNG writer: zlib on the host (filter 0, level 6) or the device encoder (adaptive filters, "
+                         "run matches; only compressed bytes leave the GPU)")
     return ap
 
 
@@ -234,7 +264,7 @@ def main(argv=None):
                 continue
             idx = args.view_index if args.view_index >= 0 else int(torch.randint(0, len(views), (1,)).item())
             done.append(render_set(args.model_path, name, it, args.mode, views, gaussians, deform, bg, args.is_6dof,
-                                   view_index=idx, frames=args.frames, chunk=args.chunk))
+                                   view_index=idx, frames=args.frames, chunk=args.chunk, png=args.png))
     return done
 
 

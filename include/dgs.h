@@ -486,6 +486,24 @@ int dgs_jpeg_coefficients(const uint8_t *bytes, size_t len, const dgs_jpeg_info 
 int dgs_ingest_jpeg(int B, int W, int H, int hs, int vs, const int16_t *coef, const uint16_t *qtables,
                     uint8_t *rgb8_out, uint8_t *scratch, void *stream);
 
+/* ---- PNG output: row filters + deflate on the device (csrc/png_encode.hip) ----
+ * dgs_png_encode: in = F frames of (H, W, C) bytes, C 3 (RGB) or 1 (grey), on the device. out receives F zlib
+ * streams back to back, each the body of one IDAT chunk of an 8-bit non-interlaced PNG of that frame: header
+ * 78 01, deflate blocks, Adler-32. out_offsets / out_lengths (device, F int64 each): where frame f's stream
+ * starts in out and its byte count; offsets ascend and the streams touch, so out[0 .. offsets[F-1] + lengths[F-1])
+ * is all of them. Rows take the cheapest of the five filter types by the sum of |residual as int8|, ties toward
+ * the lower type. The filtered stream of a frame is deflated in independent 32 KiB segments: one dynamic-Huffman
+ * block of literals and distance-1 matches each, byte-aligned by an empty stored block, or one stored block where
+ * that is smaller. out holds dgs_png_out_capacity bytes (every segment stored), scratch (16-byte aligned)
+ * dgs_png_encode_scratch_bytes; both are 0 for arguments dgs_png_encode refuses. Four launches on `stream`, no
+ * host synchronisation; the bytes depend on the input alone.
+ * DGS_ERR_ARGS: C not 1 or 3, a size below 1 or above 65536, a null pointer, misaligned scratch.
+ * DGS_ERR_UNSUPPORTED: more than 2^22 segments in one call (encode in chunks). */
+size_t dgs_png_encode_scratch_bytes(int F, int H, int W, int C);
+size_t dgs_png_out_capacity(int F, int H, int W, int C);
+int dgs_png_encode(int F, int H, int W, int C, const uint8_t *in, uint8_t *out, int64_t *out_offsets,
+                   int64_t *out_lengths, uint8_t *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
