@@ -145,6 +145,10 @@ _SIGS = {
     "dgs_png_encode_scratch_bytes": ([I, I, I, I], SZ),
     "dgs_png_out_capacity": ([I, I, I, I], SZ),
     "dgs_png_encode": ([I, I, I, I, P, P, P, P, P, P], I),
+    # JPEG output: (F, H, W, hs, vs) / (F, H, W, hs, vs, in, qtables (host), out, out_capacity, out_offsets,
+    # out_lengths, out_flags, scratch, stream): deformgs/jpeg_gpu.py
+    "dgs_jpeg_encode_scratch_bytes": ([I, I, I, I, I], SZ),
+    "dgs_jpeg_encode": ([I, I, I, I, I, P, P, P, SZ, P, P, P, P, P], I),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -7,7 +7,11 @@ from the blend kernel) and writes <MODEL>/<train|test>/<mode dir>_<k>/renders/%0
 for mode render, gt/%05d.png — the reference's directory names — with the stdlib PNG writer (--png zlib, the
 default) or the device encoder of deformgs/png_gpu.py (--png gpu: the same pixels, smaller files). Prints the
 reference's FPS line for every set (frames / elapsed of the render_frames call between two device
-synchronisations). No video is written (MP4 encoding is out of scope).
+synchronisations). --video mjpeg writes, in the five interpolation modes, renders/video.avi beside the PNGs: the
+reference's imageio video (render_baseline.py: fps 30 for time / view / all, 60 for pose / original) as Motion-JPEG
+in an AVI container (deformgs/mjpeg.py), its frames encoded on the device chunk by chunk from the same rgb8 frames
+(deformgs/jpeg_gpu.py; --video_quality, --video_subsampling). Mode render writes no video, as the reference writes
+none there. MP4 / H.264 is out of scope (it needs an encoder library).
 
 Cameras: --synthetic N takes the synthetic scene of deformgs/train.py (N Gaussians, --res W H); when MODEL
 holds no saved model yet, the scene's own initial Gaussians and a fresh network (heads at 1/100 scale) are
@@ -172,6 +176,21 @@ def frame_cameras(mode, views, view_index=0, frames=None):
     return cams, [t for _, _, t in fl]
 
 
+VIDEO_FPS = {"time": 30, "view": 30, "all": 30, "pose": 60, "original": 60}  # render_baseline.py's mimwrite calls
+
+
+def _write_video(path, rgb, fps, chunk, quality, subsampling):
+    """renders/video.avi from the rgb8 frames: JPEG on the device in chunks of frames, the container on the host."""
+    from .jpeg_gpu import encode_frames
+    from .mjpeg import write_avi
+    from .render_frames import default_chunk
+    n = int(chunk) if chunk else default_chunk(rgb.shape[1], rgb.shape[2], ("rgb8", "depth8"))
+    jpegs = []
+    for k in range(0, rgb.shape[0], n):
+        jpegs += encode_frames(rgb[k:k + n], quality=quality, subsampling=subsampling)
+    write_avi(path, jpegs, rgb.shape[2], rgb.shape[1], fps)
+
+
 def _write_gpu(out, cams, dirs, chunk):
     """--png gpu: renders, depth and the 8-bit ground truth go through deformgs.png_gpu in chunks of frames; only
     compressed bytes reach the host."""
@@ -192,12 +211,16 @@ def _write_gpu(out, cams, dirs, chunk):
 
 
 def render_set(model_path, name, iteration, mode, views, gaussians, deform, background, is_6dof, view_index=0,
-               frames=None, chunk=None, png="zlib"):
+               frames=None, chunk=None, png="zlib", video="none", video_quality=90, video_subsampling="4:2:0"):
     """Renders one camera set for `mode`, writes the PNGs, prints the FPS line. -> the output directory.
-    png: "zlib" writes with deformgs.png.write_png from host copies of the frames, "gpu" with deformgs.png_gpu."""
+    png: "zlib" writes with deformgs.png.write_png from host copies of the frames, "gpu" with deformgs.png_gpu.
+    video: "mjpeg" also writes renders/video.avi in an interpolation mode (nothing in mode render); "none" writes
+    what was written before the option existed."""
     from .render_frames import render_frames
     if png not in ("zlib", "gpu"):
         raise ValueError(f"render_set: png must be 'zlib' or 'gpu', got {png!r}")
+    if video not in ("none", "mjpeg"):
+        raise ValueError(f"render_set: video must be 'none' or 'mjpeg', got {video!r}")
     base = os.path.join(model_path, name, f"{DIR_NAMES[mode]}_{iteration}")
     dirs = {k: os.path.join(base, k) for k in (("renders", "depth", "gt") if mode == "render" else ("renders", "depth"))}
     for d in dirs.values():
@@ -221,6 +244,9 @@ def render_set(model_path, name, iteration, mode, views, gaussians, deform, back
                 gt = cams[i].original_image[0:3]
                 gt8 = (255 * gt.clamp(0, 1)).to(torch.uint8).permute(1, 2, 0).contiguous().cpu().numpy()
                 write_png(os.path.join(dirs["gt"], f"{i:05d}.png"), gt8)
+    if video == "mjpeg" and mode in VIDEO_FPS and cams:
+        _write_video(os.path.join(dirs["renders"], "video.avi"), out["rgb8"], VIDEO_FPS[mode], chunk, video_quality,
+                     video_subsampling)
     fps = len(cams) / dt if dt > 0 and cams else 0.0
     print(f"Test FPS: \033[1;35m{fps:.5f}\033[0m, Num. of GS: {gaussians.get_xyz.shape[0]}", flush=True)
     return base
@@ -250,6 +276,11 @@ def build_parser():
     ap.add_argument("--png", choices=["zlib", "gpu"], default="zlib",
                     help="the PNG writer: zlib on the host (filter 0, level 6) or the device encoder (adaptive filters, "
                          "run matches; only compressed bytes leave the GPU)")
+    ap.add_argument("--video", choices=["none", "mjpeg"], default="none",
+                    help="mjpeg: the interpolation modes also write renders/video.avi (Motion-JPEG, frames encoded on the "
+                         "device; 30 fps for time / view / all, 60 for pose / original)")
+    ap.add_argument("--video_quality", type=int, default=90, help="JPEG quality of the video's frames, 1..100")
+    ap.add_argument("--video_subsampling", choices=["4:4:4", "4:2:2", "4:2:0"], default="4:2:0")
     return ap
 
 
@@ -264,7 +295,9 @@ def main(argv=None):
                 continue
             idx = args.view_index if args.view_index >= 0 else int(torch.randint(0, len(views), (1,)).item())
             done.append(render_set(args.model_path, name, it, args.mode, views, gaussians, deform, bg, args.is_6dof,
-                                   view_index=idx, frames=args.frames, chunk=args.chunk, png=args.png))
+                                   view_index=idx, frames=args.frames, chunk=args.chunk, png=args.png,
+                                   video=args.video, video_quality=args.video_quality,
+                                   video_subsampling=args.video_subsampling))
     return done
 
 

@@ -504,6 +504,35 @@ size_t dgs_png_out_capacity(int F, int H, int W, int C);
 int dgs_png_encode(int F, int H, int W, int C, const uint8_t *in, uint8_t *out, int64_t *out_offsets,
                    int64_t *out_lengths, uint8_t *scratch, void *stream);
 
+/* ---- baseline JPEG output: the inverse of dgs_ingest_jpeg, on the device (csrc/jpeg_encode.hip) ----
+ * dgs_jpeg_encode: in = F frames of (H, W, 3) RGB bytes on the device. out receives, per frame, the entropy-coded
+ * data of a baseline (SOF0) YCbCr JPEG with luma sampling hs x vs = 1x1 (4:4:4), 2x1 (4:2:2) or 2x2 (4:2:0) and
+ * chroma 1x1: one interleaved scan, the four Huffman tables of ITU-T T.81 Annex K.3 (compiled in), a restart
+ * interval of one MCU row: every MCU row starts with zero DC predictors, ends padded with one bits to a byte, 0xFF
+ * is followed by a stuffed 0x00, and RSTm (m = row index mod 8) stands between the rows. The caller writes the
+ * markers before it (with DRI = the MCUs of a row) and EOI behind it (deformgs/jpeg_gpu.py).
+ * The arithmetic is libjpeg-turbo's default compressor in integers, what PIL's Image.save(quality=q, optimize=False)
+ * runs: jccolor.c's RGB -> YCbCr in 16-bit fixed point, jcsample.c's h2v1 / h2v2 box downsampling (edges replicated
+ * to the component's block-padded size), level shift, jfdctint.c's 8x8 forward DCT, quantisation against qtable << 3
+ * rounding half away from zero; blocks that only fill an MCU beyond the component's own block-padded size are
+ * jccoefct.c's dummy blocks (AC zero, DC of the block before). qtables: HOST pointer, (2, 64) uint16 in natural
+ * order, luma then chroma, read before the call returns. The quantised coefficients stay at the start of scratch in
+ * the layout of dgs_jpeg_coefficients, frame after frame.
+ * out_offsets / out_lengths (device, F int64 each): where frame f's data starts in out and its byte count; the
+ * frames touch and the lengths are the true ones whatever out_capacity is. Nothing is written at or past
+ * out + out_capacity: a frame that does not fit whole is not written, and out_flags[f] (device, F ints) is 1 for it,
+ * 0 for a frame that is there. A fresh call with out_offsets[F-1] + out_lengths[F-1] bytes of room produces all.
+ * scratch (16-byte aligned) holds dgs_jpeg_encode_scratch_bytes, 0 for arguments dgs_jpeg_encode refuses. Four
+ * launches on `stream` (the entropy coder runs twice: once to size the segments, once to write them in place), no
+ * host synchronisation, no global atomics; the bytes depend on the input alone.
+ * DGS_ERR_ARGS: a null pointer, a size below 1 or above 65535 (the SOF0 field), sampling other than the three
+ * above, a zero in a quantisation table, misaligned scratch.
+ * DGS_ERR_UNSUPPORTED: more than 2^22 MCU rows or 2^36 blocks in one call (encode in chunks). */
+size_t dgs_jpeg_encode_scratch_bytes(int F, int H, int W, int hs, int vs);
+int dgs_jpeg_encode(int F, int H, int W, int hs, int vs, const uint8_t *in, const uint16_t *qtables, uint8_t *out,
+                    size_t out_capacity, int64_t *out_offsets, int64_t *out_lengths, int *out_flags, uint8_t *scratch,
+                    void *stream);
+
 #ifdef __cplusplus
 }
 #endif
