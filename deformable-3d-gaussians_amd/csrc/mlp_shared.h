@@ -1,5 +1,5 @@
 // Pieces shared by the two deformation-MLP paths: mlp.hip (fp32 MFMA, DGS_MLP_EXACT_FP32) and
-// mlp_split.hip (the default: bf16 MFMA on an exact three-way operand split).
+// mlp_split.hip (the default: f16 MFMA on a scaled two-piece operand split).
 //
 // Network shape (utils/time_utils.py:56-127, DeformNetwork :129-201): D=8, W=256, multires=10,
 // skips=[4]; blender adds timenet Linear(13,256)+ReLU+Linear(256,30); heads d_xyz(3) | 6-DoF

@@ -138,6 +138,30 @@ def test_expanded_time_input():
     assert torch.allclose(a, b, rtol=1e-5, atol=1e-6 * float(b.abs().max()))
 
 
+@pytest.mark.parametrize("tmode", ["expanded", "random"])
+@pytest.mark.parametrize("N", [63, 4099])
+def test_mlp_inference_forward_vs_oracle(tmode, N):
+    """The forward without saved activations (torch.no_grad, as renderer.py calls it): k_fwd<false, true>
+    for a stride-0 frame time (DGS_MLP_UNIFORM_T, t_emb folded into the biases) and k_fwd<false, false>
+    for per-point times, against the float64 oracle at the training forward's tolerance. N = 63: one
+    partial 64-point block; N = 4099: 64 full blocks plus a 3-point block (padding, block loop, hand-off
+    chain)."""
+    net, w = _net("blender", 77)
+    rng = np.random.default_rng(N)
+    x = rng.uniform(-1.3, 1.3, (N, 3)).astype(np.float32)
+    if tmode == "expanded":
+        t = np.full((N, 1), 0.37, np.float32)
+        tt = torch.full((1, 1), 0.37, device="cuda").expand(N, -1)
+    else:
+        t = _times(rng, N, "random")
+        tt = torch.from_numpy(t).cuda()
+    out, _ = mlp_ref.forward(w, x, t, True, False)
+    with torch.no_grad():
+        d_xyz, d_rot, d_scale = net(torch.from_numpy(x).cuda(), tt)
+    for a, b in ((d_xyz, out["d_xyz"]), (d_rot, out["d_rot"]), (d_scale, out["d_scale"])):
+        assert np.allclose(a.cpu().numpy(), b, atol=2e-5, rtol=1e-4)
+
+
 @pytest.mark.parametrize("name,N", [("blender", 20000), ("nonblender", 20000), ("6dof", 20000), ("fork", 20000),
                                     ("blender", 100000)])
 def test_split_accuracy_matches_fp32(name, N):

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Alternating bench runs over several environment variants (';'-separated; "default" = none):
-#   ENVS="default;DGS_MLP_BWD8=1;DGS_MLP_FWD8=0" [RUNS=3] [TIMING=all] tools/env_abn.sh
+#   ENVS="default;DGS_MLP_NO_TAIL=1;DGS_MLP_STATIC=1" [RUNS=3] [TIMING=all] tools/env_abn.sh
 set -u
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out

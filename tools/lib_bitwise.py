@@ -4,7 +4,8 @@ keeps every output tile's summation order must reproduce the previous build's bi
   python3 tools/lib_bitwise.py dump OUT.npz      (with DGS_LIB=... selecting the build)
   python3 tools/lib_bitwise.py cmp A.npz B.npz
 The dump runs DeformNetworkBaseline forward + backward (blender and non-blender; frame-uniform t and
-per-point t; ragged N) and stores the outputs and every parameter gradient."""
+per-point t; ragged N), then the same forward under torch.no_grad (the inference kernels), and stores
+the outputs and every parameter gradient."""
 import os
 import sys
 
@@ -33,6 +34,11 @@ def dump(path):
                     out[f"{key}/{name}"] = v.detach().cpu().numpy()
                 for name, p in net.named_parameters():
                     out[f"{key}/g_{name}"] = p.grad.detach().cpu().numpy()
+                # the inference forward (no saved activations): the folded-t_emb kernel for the stride-0
+                # t (DGS_MLP_UNIFORM_T, as renderer.py calls it), the per-point kernel otherwise
+                with torch.no_grad():
+                    for name, v in zip(("d_xyz", "d_rot", "d_s"), net(x, t)):
+                        out[f"{key}/nograd_{name}"] = v.cpu().numpy()
     np.savez(path, **out)
     print(f"dumped {len(out)} arrays to {path}")
 
