@@ -1,5 +1,6 @@
-// Pieces shared by the two deformation-MLP paths: mlp.hip (fp32 MFMA, DGS_MLP_EXACT_FP32) and
-// mlp_split.hip (the default: f16 MFMA on a scaled two-piece operand split).
+// Pieces shared by the two deformation-MLP paths: mlp.hip with mlp_fp32_*.h / mlp_dw_*.h (fp32 MFMA,
+// DGS_MLP_EXACT_FP32) and mlp_split.hip with mlp_split_*.h (the default: f16 MFMA on a scaled
+// two-piece operand split).
 //
 // Network shape (utils/time_utils.py:56-127, DeformNetwork :129-201): D=8, W=256, multires=10,
 // skips=[4]; blender adds timenet Linear(13,256)+ReLU+Linear(256,30); heads d_xyz(3) | 6-DoF
@@ -262,7 +263,7 @@ inline WPlan make_wplan(const Flags &F, int target, double fixed, double floor_,
     return W;
 }
 
-// Sums every parameter gradient out of the dW slabs in a fixed order (mlp.hip: k_dw_reduce), one
+// Sums every parameter gradient out of the dW slabs in a fixed order (mlp_dw_reduce.h: k_dw_reduce), one
 // launch for all parameters. grads: device pointers in state_dict order.
 int launch_dw_reduce(const Flags &F, const WPlan &W, const float *slabs, float *const *grads, hipStream_t stream);
 
@@ -316,7 +317,7 @@ __device__ inline TileAddr tile_addr(const float *dst, size_t Ns, int row0, int 
 
 }  // namespace mlpc
 
-// fp32-MFMA path (mlp.hip), selected by DGS_MLP_EXACT_FP32
+// fp32-MFMA path (host side in mlp.hip, kernels in mlp_fp32_*.h), selected by DGS_MLP_EXACT_FP32
 namespace mlp {
 size_t packed_floats(int flags);
 size_t saved_floats(int flags, int N);
@@ -326,7 +327,7 @@ int forward(int flags, int N, const float *xyz, const float *t, const float *pac
             hipStream_t stream);
 int backward(int flags, int N, const float *packed, const float *saved, const float *dout, float *scratch,
              float *const *grads, hipStream_t stream);
-// dW (fp32-input MFMA) + reduction over [rows][Ns] dZ / saved arrays; slabs: dw_fp32_slab_floats
+// dW (fp32-input MFMA, mlp_dw_fp32.h: k_dw) + reduction (mlp_dw_reduce.h) over [rows][Ns] dZ / saved arrays; slabs: dw_fp32_slab_floats
 size_t dw_fp32_slab_floats(int flags);
 int dw_fp32(const mlpc::Flags &F, size_t Ns, const float *dz, const float *saved, float *slabs, float *const *grads,
             hipStream_t stream);

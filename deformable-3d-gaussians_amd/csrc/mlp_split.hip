@@ -1,6 +1,6 @@
 // Fused deformation MLP (positional encoding + timenet + 8x256 trunk with skip + heads) on f16 MFMA
 // with a scaled two-piece operand split: the default path of dgs_deform_* (the fp32-MFMA kernels of
-// mlp.hip run instead under DGS_MLP_EXACT_FP32).
+// mlp.hip / mlp_fp32_*.h run instead under DGS_MLP_EXACT_FP32).
 //
 // Replaces DeformNetworkBaseline.forward and its autograd backward (utils/time_utils.py:56-127;
 // DeformNetwork :129-201 via DGS_MLP_NO_ROTSCALE; 6-DoF heads :114-121 emitted raw, exp_se3 stays in
@@ -191,7 +191,7 @@ size_t saved_floats(int flags, int N) {
 }
 
 // dW arithmetic (DGS_MLP_SPLIT_DW): 3 (default) = the split-f16 k_dws (private / shared operands, every
-// value split once), 0 = the fp32-input MFMA k_dw of mlp.hip, both on the same [rows][Ns] arrays (the
+// value split once), 0 = the fp32-input MFMA k_dw (mlp_dw_fp32.h, via mlp::dw_fp32), both on the same [rows][Ns] arrays (the
 // bf16 k_dw / k_dwg variants, modes 1 and 2, were removed with the bf16x6 arithmetic in round 6)
 static int dw_mode() {
     static const int m = env_starts("DGS_MLP_SPLIT_DW", '0') ? 0 : 3;

@@ -30,7 +30,7 @@ namespace mlps {
 // fp32's own rounding of T).
 //   Output: ROW jobs' tiles are [dZ row][X row] (the slab's own layout, stored as before); COL jobs'
 // are [X row][dZ row] and go through a per-wave LDS transpose so the slab stores stay coalesced.
-// Same job plan, slab layout and k_dw_reduce as the fp32 k_dw.
+// Same job plan, slab layout and k_dw_reduce (mlp_dw_reduce.h) as the fp32 k_dw (mlp_dw_fp32.h).
 // ------------------------------------------------------------------------------------------------
 constexpr int DW_THREADS = 512;
 constexpr int S_UNITS = NSPLIT * 2 * 8 * 64;  // 16-B units per chunk buffer

@@ -140,13 +140,16 @@ def test_expanded_time_input():
 
 @pytest.mark.parametrize("tmode", ["expanded", "random"])
 @pytest.mark.parametrize("N", [63, 4099])
-def test_mlp_inference_forward_vs_oracle(tmode, N):
-    """The forward without saved activations (torch.no_grad, as renderer.py calls it): k_fwd<false, true>
-    for a stride-0 frame time (DGS_MLP_UNIFORM_T, t_emb folded into the biases) and k_fwd<false, false>
-    for per-point times, against the float64 oracle at the training forward's tolerance. N = 63: one
-    partial 64-point block; N = 4099: 64 full blocks plus a 3-point block (padding, block loop, hand-off
-    chain)."""
-    net, w = _net("blender", 77)
+@pytest.mark.parametrize("arith", list(ARITH))
+def test_mlp_inference_forward_vs_oracle(tmode, N, arith):
+    """The forward without saved activations (torch.no_grad, as renderer.py calls it), against the float64
+    oracle at the training forward's tolerance (test_mlp_vs_oracle_ragged's, the same for both arithmetics).
+    split: k_fwd<false, true> for a stride-0 frame time (DGS_MLP_UNIFORM_T, t_emb folded into the biases)
+    and k_fwd<false, false> for per-point times; N = 63: one partial 64-point block; N = 4099: 64 full
+    blocks plus a 3-point block (padding, block loop, hand-off chain). exact: k_mlp_fwd<false> (the fp32
+    path has no folded kernel: both t modes run the per-point timenet); N = 63: two 32-point blocks, the
+    second ragged; N = 4099: 129 blocks, the last with 3 points."""
+    net, w = _net("blender", 77, ARITH[arith])
     rng = np.random.default_rng(N)
     x = rng.uniform(-1.3, 1.3, (N, 3)).astype(np.float32)
     if tmode == "expanded":

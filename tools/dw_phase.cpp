@@ -1,6 +1,7 @@
-// Diagnostic: per-wave timing of k_dw chunks (built with -DDGS_MLP_PROFILE).
-// Build: hipcc -O3 --offload-arch=gfx950 -DDGS_MLP_PROFILE -munsafe-fp-atomics -I include \
-//        tools/dw_phase.cpp deformable-3d-gaussians_amd/csrc/mlp.hip deformable-3d-gaussians_amd/csrc/api.hip -o tools/dw_phase.bin
+// Diagnostic: per-wave timing of k_dw chunks (mlp_dw_fp32.h, built with -DDGS_MLP_PROFILE), on the fp32 path.
+// Build: hipcc -O3 -std=c++17 --offload-arch=gfx950 -DDGS_MLP_PROFILE -munsafe-fp-atomics -I include \
+//        tools/dw_phase.cpp deformable-3d-gaussians_amd/csrc/mlp.hip deformable-3d-gaussians_amd/csrc/mlp_split.hip \
+//        deformable-3d-gaussians_amd/csrc/api.hip -o tools/dw_phase.bin
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -12,7 +13,7 @@
 extern "C" void dgs_mlp_set_prof(unsigned long long *p);
 
 int main() {
-    const int N = 100000, flags = DGS_MLP_BLENDER;
+    const int N = 100000, flags = DGS_MLP_BLENDER | DGS_MLP_EXACT_FP32;
     const size_t npk = dgs_deform_packed_floats(flags), nsv = dgs_deform_saved_floats(flags, N);
     const size_t nsc = dgs_deform_scratch_floats(flags, N);
     float *pk, *x, *t, *out, *saved, *dout, *scratch, *gbuf;
