@@ -30,9 +30,6 @@
 //                        sort on the tile bits, k_ranges
 //   DGS_TILE_SORT=0      global depth order: radix sort of the Gaussians by depth key (radix.hip), then
 //                        rect binning over that order and no k_tile_sort
-//   DGS_HIPCUB_SORT=1    hipcub radix sorts instead of radix.hip (implies sort binning)
-//   DGS_BLEND_SEG=1      k_blend_bwd2s: segmented blend backward from checkpoints k_blend_fwd<true> leaves
-//   DGS_BLEND_FWD2=1     k_blend_fwd2: the two-pixels-per-lane forward blend
 //   DGS_DETERMINISTIC=1  k_blend_bwd2<.., true> + k_rect_gather: per-pair slots summed in a fixed order
 #include <hip/hip_runtime.h>
 
@@ -44,7 +41,7 @@
 #include <map>
 #include <atomic>
 #include <mutex>
-#include <tuple>
+#include <utility>
 #include <vector>
 
 #include "radix.h"
@@ -90,14 +87,8 @@ struct dgs_raster_ctx {
     // (re)allocated, so it only ever holds 0 or words a colscan launch wrote (never stale count-matrix
     // data whose upper half could equal the current generation)
     DevBuf rtot;
-    // segmented blend backward (DGS_BLEND_SEG): the forward's per-pixel checkpoints every SEG list
-    // positions, and [work queue (2) | maxtodo | - | tile_todo (T)] (zeroed when (re)allocated; the
-    // queue resets itself at the end of every launch, maxtodo is zeroed by k_rect_count)
-    DevBuf ckb, segq;
     // deterministic blend backward (dgs_raster_set_deterministic): [tile_todo (T, padded) | per-pair slots]
     DevBuf det;
-    bool seg_ok = false;  // this forward wrote the checkpoints
-    float4 *cfin = nullptr;  // the forward's final (T, C) per pixel (segmented backward)
     bool bwd_done = false;  // a backward already consumed the accumulators (a second one re-zeroes them)
     // carved views
     float2 *xy = nullptr;
@@ -132,35 +123,20 @@ std::vector<dgs_raster_ctx *> g_pool;
 
 size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
-// DGS_HIPCUB_SORT=1: hipcub::DeviceRadixSort for the depth and tile sorts instead of radix.hip
-bool hipcub_sort() {
-    static const bool v = env_starts("DGS_HIPCUB_SORT", '1');
-    return v;
-}
-
-// DGS_BLEND_SEG=1 / dgs_debug_set_blend_seg: segmented blend backward (k_blend_bwd2s: SEG-long segments of
-// every tile's list as independent work items, from checkpoints the forward leaves) instead of
-// k_blend_bwd2's one serial replay per tile
-Toggle g_blend_seg{[] { return env_starts("DGS_BLEND_SEG", '1'); }};
-
 // DGS_DETERMINISTIC=1 / dgs_raster_set_deterministic(1): the blend backward (rect binning) writes per-pair
 // slots that k_rect_gather sums in a fixed order instead of float atomics into acc: bitwise reproducible
 // gradients at the cost of the slot traffic (96 B per pair written and read)
 Toggle g_det{[] { return env_starts("DGS_DETERMINISTIC", '1'); }};
 
-// DGS_BLEND_FWD2=1 / dgs_debug_set_blend_fwd2: the two-pixels-per-lane forward blend (k_blend_fwd2)
-Toggle g_fwd2{[] { return env_starts("DGS_BLEND_FWD2", '1'); }};
-
 // DGS_TILE_SORT=0 / dgs_debug_set_tile_sort(0): rect binning over the global depth sort's order (k_rect_*
 // on depth-ordered Gaussians) instead of index order + the per-tile depth sort (k_tile_sort, the default)
 Toggle g_tile_sort{[] { return !env_starts("DGS_TILE_SORT", '0'); }};
 
-// DGS_BINNING=sort (or DGS_HIPCUB_SORT=1) / dgs_debug_set_binning(1): duplicate + tile-key radix sort +
-// ranges for every image, instead of rect binning up to RECT_MAX_TILES tiles and RECT_MAX_CELLS
-// count-matrix cells (the default)
+// DGS_BINNING=sort / dgs_debug_set_binning(1): duplicate + tile-key radix sort + ranges for every image,
+// instead of rect binning up to RECT_MAX_TILES tiles and RECT_MAX_CELLS count-matrix cells (the default)
 Toggle g_sort_binning{[] {
     const char *e = getenv("DGS_BINNING");
-    return (e && strcmp(e, "sort") == 0) || hipcub_sort();
+    return e && strcmp(e, "sort") == 0;
 }};
 
 // process-wide launch generations of k_rect_colscan: a tag never repeats across contexts whose
@@ -178,11 +154,11 @@ bool rect_binning(int gx, int gy, int P) {
            (long long)div_up(P, 256) * T <= RECT_MAX_CELLS;
 }
 
-// hipcub temp-storage sizes, cached per (device, size class): the size queries cost tens of us of
-// host time each inside the num_rendered sync window. Sizes are queried for the class's upper end
-// (temp storage grows monotonically with the item count).
+// The hipcub scan's temp-storage size (sort binning), cached per (device, size class): the size query
+// costs tens of us of host time inside the num_rendered sync window. Sizes are queried for the class's
+// upper end (temp storage grows monotonically with the item count).
 std::mutex g_tmp_mu;
-std::map<std::tuple<int, int, int, int>, size_t> g_tmp_sizes;  // (kind, device, class, end_bit)
+std::map<std::pair<int, int>, size_t> g_tmp_sizes;  // (device, class)
 
 int size_class(int n) {  // 1/16-octave classes
     if (n <= 4096) return 0;
@@ -226,26 +202,11 @@ void pair_cap_observe(int device, int nr) {
 hipError_t scan_tmp_bytes(int device, int P, hipStream_t stream, size_t &bytes) {
     const int cls = size_class(P);
     std::lock_guard<std::mutex> lk(g_tmp_mu);
-    auto key = std::make_tuple(0, device, cls, 0);
+    const auto key = std::make_pair(device, cls);
     auto it = g_tmp_sizes.find(key);
     if (it != g_tmp_sizes.end()) { bytes = it->second; return hipSuccess; }
     hipError_t e = hipcub::DeviceScan::InclusiveSum(nullptr, bytes, (uint32_t *)nullptr, (uint32_t *)nullptr,
                                                     class_upper(cls), stream);
-    if (e == hipSuccess) g_tmp_sizes[key] = bytes;
-    return e;
-}
-
-// radix-sort temp bytes for (KT keys, u32 values), cached per (key type, device, size class, bits)
-template <class KT>
-hipError_t sort_tmp_bytes(int device, int n, int end_bit, hipStream_t stream, size_t &bytes) {
-    const int cls = size_class(n);
-    std::lock_guard<std::mutex> lk(g_tmp_mu);
-    auto key = std::make_tuple((int)sizeof(KT), device, cls, end_bit);
-    auto it = g_tmp_sizes.find(key);
-    if (it != g_tmp_sizes.end()) { bytes = it->second; return hipSuccess; }
-    hipcub::DoubleBuffer<KT> kb(nullptr, nullptr);
-    hipcub::DoubleBuffer<uint32_t> vb(nullptr, nullptr);
-    hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, kb, vb, class_upper(cls), 0, end_bit, stream);
     if (e == hipSuccess) g_tmp_sizes[key] = bytes;
     return e;
 }
@@ -348,15 +309,12 @@ static int wait_count_impl(dgs_raster_ctx *c, hipStream_t stream, int &nr) {
 // the stable order of the real pairs untouched), bounded duplicate in depth order, stable radix sort
 // of cap items on the tile bits, ranges from the device-side count, forward blend.
 template <class KT>
-static int bin_tiles(dgs_raster_ctx *c, int cap, int P, int device, hipStream_t stream, bool dbg) {
+static int bin_tiles(dgs_raster_ctx *c, int cap, int P, hipStream_t stream, bool dbg) {
     const int T = c->gx * c->gy;
     const int end_bit = bits_for((uint32_t)T);
-    const bool cub = hipcub_sort();
-    size_t sort_tmp = 0;
-    if (cub) DGS_HIP_CHECK(sort_tmp_bytes<KT>(device, cap, end_bit, stream, sort_tmp));
     size_t o_k0 = 0, o_k1 = align_up(sizeof(KT) * cap), o_v0 = align_up(o_k1 + sizeof(KT) * cap),
-           o_v1 = align_up(o_v0 + 4ull * cap), o_t = align_up(o_v1 + 4ull * cap);
-    if (int rc = c->bin.ensure(o_t + sort_tmp + 256)) return rc;
+           o_v1 = align_up(o_v0 + 4ull * cap);
+    if (int rc = c->bin.ensure(align_up(o_v1 + 4ull * cap) + 256)) return rc;
     char *b = (char *)c->bin.p;
     KT *k0 = (KT *)(b + o_k0), *k1 = (KT *)(b + o_k1);
     uint32_t *v0 = (uint32_t *)(b + o_v0), *v1 = (uint32_t *)(b + o_v1);
@@ -369,18 +327,10 @@ static int bin_tiles(dgs_raster_ctx *c, int cap, int P, int device, hipStream_t 
     KT *ksorted = k0;
     {
         ScopedTimer tm("sort", stream);
-        if (cub) {
-            hipcub::DoubleBuffer<KT> kbuf(k0, k1);
-            hipcub::DoubleBuffer<uint32_t> vbuf(v0, v1);
-            DGS_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(b + o_t, sort_tmp, kbuf, vbuf, cap, 0, end_bit, stream));
-            c->vals = vbuf.Current();
-            ksorted = kbuf.Current();
-        } else {
-            int alt = 0;
-            if (int rc = radix::sort_pairs<KT>(k0, k1, v0, v1, cap, end_bit, stream, &alt)) return rc;
-            c->vals = alt ? v1 : v0;
-            ksorted = alt ? k1 : k0;
-        }
+        int alt = 0;
+        if (int rc = radix::sort_pairs<KT>(k0, k1, v0, v1, cap, end_bit, stream, &alt)) return rc;
+        c->vals = alt ? v1 : v0;
+        ksorted = alt ? k1 : k0;
     }
     {
         ScopedTimer tm("ranges", stream);
@@ -406,7 +356,7 @@ static int det_layout(dgs_raster_ctx *c, int cap, uint32_t **tile_end, float **s
 }
 
 // The tile lists (c->ranges, c->vals) for `cap` pairs: shared by the training forward and dgs_render_frames
-static int bin_lists(dgs_raster_ctx *c, int cap, int P, int device, hipStream_t stream, bool dbg) {
+static int bin_lists(dgs_raster_ctx *c, int cap, int P, hipStream_t stream, bool dbg) {
     const int T = c->gx * c->gy;
     if (c->rect_mode) {
         // tile sort: the lists, then 8 + 4 (+ 4: the deterministic mode's copy) bytes of scratch per pair for
@@ -440,8 +390,7 @@ static int bin_lists(dgs_raster_ctx *c, int cap, int P, int device, hipStream_t 
         }
     } else if (cap > 0) {  // k_duplicate clears c->ranges
         // 16-bit tile keys up to 65535 tiles (4080 x 4080 pixels), 32-bit beyond
-        const int rc = T < 65535 ? bin_tiles<uint16_t>(c, cap, P, device, stream, dbg)
-                                 : bin_tiles<uint32_t>(c, cap, P, device, stream, dbg);
+        const int rc = T < 65535 ? bin_tiles<uint16_t>(c, cap, P, stream, dbg) : bin_tiles<uint32_t>(c, cap, P, stream, dbg);
         if (rc) return rc;
     } else {
         DGS_HIP_CHECK(hipMemsetAsync(c->ranges, 0, 8ull * T, stream));
@@ -450,29 +399,14 @@ static int bin_lists(dgs_raster_ctx *c, int cap, int P, int device, hipStream_t 
     return DGS_OK;
 }
 
-static int bin_and_blend(dgs_raster_ctx *c, int cap, int P, int device, hipStream_t stream, bool dbg, float *out_color,
+static int bin_and_blend(dgs_raster_ctx *c, int cap, int P, hipStream_t stream, bool dbg, float *out_color,
                          float *out_depth) {
-    const int T = c->gx * c->gy;
-    if (int rc = bin_lists(c, cap, P, device, stream, dbg)) return rc;
-    float4 *ckpt = nullptr, *cfin = nullptr;
-    uint32_t *todo = nullptr;
-    if (c->seg_ok) {
-        const size_t nck = (size_t)TILE_PIX * ((size_t)std::max(cap, 0) / SEG + 4);
-        if (int rc = c->ckb.ensure(16ull * (nck + (size_t)c->H * c->W))) return rc;
-        ckpt = (float4 *)c->ckb.p;
-        cfin = ckpt + nck;
-        c->cfin = cfin;
-        todo = (uint32_t *)c->segq.p + 4;
-    }
-    if (!ckpt && g_fwd2.get()) {
+    if (int rc = bin_lists(c, cap, P, stream, dbg)) return rc;
+    {
         ScopedTimer tm("blend_fwd", stream);
-        hipLaunchKernelGGL(k_blend_fwd2, dim3(T), dim3(B2), 0, stream, c->ranges, c->vals, (uint32_t)cap, c->W, c->H, c->gx,
-                           c->xy, c->conic_o, c->rgbd, c->s.bg, c->final_T, c->n_contrib, out_color, out_depth);
-    } else {
-        ScopedTimer tm("blend_fwd", stream);
-        hipLaunchKernelGGL(ckpt ? k_blend_fwd<true> : k_blend_fwd<false>, dim3(T), dim3(TILE_PIX), 0, stream, c->ranges, c->vals, (uint32_t)cap, c->W, c->H, c->gx, c->xy,
-                           c->conic_o, c->rgbd, c->s.bg, c->final_T, c->n_contrib, out_color, out_depth, ckpt, todo,
-                           todo ? todo - 2 : nullptr, cfin);
+        hipLaunchKernelGGL(k_blend_fwd, dim3(c->gx * c->gy), dim3(TILE_PIX), 0, stream, c->ranges, c->vals, (uint32_t)cap,
+                           c->W, c->H, c->gx, c->xy, c->conic_o, c->rgbd, c->s.bg, c->final_T, c->n_contrib, out_color,
+                           out_depth);
     }
     DGS_LAUNCH_CHECK("k_blend_fwd", dbg, stream);
     return DGS_OK;
@@ -513,10 +447,10 @@ static int resolve_count(dgs_raster_ctx *c, hipStream_t stream) {
 // frame setup: the stages up to the pair count, one copy for the training forward (raster_forward) and
 // dgs_render_frames (render_raster_frame)
 // ------------------------------------------------------------------------------------------------
-// the hipcub scan / depth-sort scratch at the end of the geometry buffer
+// the hipcub scan's scratch (sort binning) at the end of the geometry buffer
 struct GeomScratch {
     char *p = nullptr;
-    size_t scan_bytes = 0, sort_bytes = 0;
+    size_t scan_bytes = 0;
 };
 
 // Size and carve c->geom for P Gaussians. The slot after `offsets` holds the forward's clamped flags
@@ -526,12 +460,9 @@ static int carve_geom(dgs_raster_ctx *c, int P, bool own_radii, hipStream_t stre
            off_t = align_up(off_cd + 16ull * P), off_o = align_up(off_t + 4ull * P), off_slot = align_up(off_o + 4ull * P);
     size_t off_dk = align_up(off_slot + (own_radii ? 4ull : 1ull) * P), off_dk2 = align_up(off_dk + 4ull * P),
            off_gid = align_up(off_dk2 + 4ull * P), off_ord = align_up(off_gid + 4ull * P), off_ts = align_up(off_ord + 4ull * P);
-    if (P > 0) {
-        DGS_HIP_CHECK(scan_tmp_bytes(c->device, P, stream, scr->scan_bytes));
-        DGS_HIP_CHECK(sort_tmp_bytes<uint32_t>(c->device, P, 32, stream, scr->sort_bytes));
-    }
+    if (P > 0) DGS_HIP_CHECK(scan_tmp_bytes(c->device, P, stream, scr->scan_bytes));
     const size_t off_st = align_up(off_ts + 4ull * P);
-    if (int rc = c->geom.ensure(off_st + std::max(scr->scan_bytes, scr->sort_bytes) + 256)) return rc;
+    if (int rc = c->geom.ensure(off_st + scr->scan_bytes + 256)) return rc;
     char *g = (char *)c->geom.p;
     c->xy = (float2 *)(g + off_xy);
     c->conic_o = (float4 *)(g + off_co);
@@ -572,36 +503,26 @@ static int carve_rect(dgs_raster_ctx *c, int P, hipStream_t stream) {
 
 // Without the per-tile sort: the Gaussians by depth (stable on the index) into c->order, and for sort
 // binning tiles[order[j]] (the scan input) into c->tiles_sorted
-static int depth_order(dgs_raster_ctx *c, int P, GeomScratch &scr, hipStream_t stream, bool dbg) {
+static int depth_order(dgs_raster_ctx *c, int P, hipStream_t stream, bool dbg) {
     if (!c->tsort) {
         ScopedTimer tm("depth_sort", stream);
-        if (hipcub_sort()) {
-            hipcub::DoubleBuffer<uint32_t> kb(c->dkey, c->dkey_alt), vb(c->gid, c->order);
-            DGS_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(scr.p, scr.sort_bytes, kb, vb, P, 0, 32, stream));
-            c->order = vb.Current();  // either buffer, per the pass count
-            hipLaunchKernelGGL(k_gather_tiles, dim3(div_up(P, 256)), dim3(256), 0, stream, P, c->order, c->tiles,
-                               c->tiles_sorted);
-        } else {
-            // the last pass also gathers tiles[order[j]] into tiles_sorted
-            int alt = 0;
-            uint32_t *gid = c->gid, *ord = c->order;
-            if (int rc = radix::sort_pairs<uint32_t>(c->dkey, c->dkey_alt, gid, ord, P, 32, stream, &alt,
-                                                     c->rect_mode ? nullptr : c->tiles,
-                                                     c->rect_mode ? nullptr : c->tiles_sorted))
-                return rc;
-            c->order = alt ? ord : gid;
-        }
+        // the last pass also gathers tiles[order[j]] into tiles_sorted
+        int alt = 0;
+        uint32_t *gid = c->gid, *ord = c->order;
+        if (int rc = radix::sort_pairs<uint32_t>(c->dkey, c->dkey_alt, gid, ord, P, 32, stream, &alt,
+                                                 c->rect_mode ? nullptr : c->tiles,
+                                                 c->rect_mode ? nullptr : c->tiles_sorted))
+            return rc;
+        c->order = alt ? ord : gid;
     }
     DGS_LAUNCH_CHECK("depth_sort", dbg, stream);
     return DGS_OK;
 }
 
-// The frame's pair count. Rect binning: k_rect_count + k_rect_colscan, which stores it through c->d_total
-// (maxtodo: the segmented backward's word that k_rect_count zeroes, or null). Sort binning: the inclusive
-// scan of tiles_sorted into c->offsets, and with `readback` its last element copied to c->h_total with
-// c->count_ev recorded behind the copy.
-static int count_pairs(dgs_raster_ctx *c, int P, GeomScratch &scr, uint32_t *maxtodo, bool readback,
-                       hipStream_t stream, bool dbg) {
+// The frame's pair count. Rect binning: k_rect_count + k_rect_colscan, which stores it through c->d_total.
+// Sort binning: the inclusive scan of tiles_sorted into c->offsets, and with `readback` its last element
+// copied to c->h_total with c->count_ev recorded behind the copy.
+static int count_pairs(dgs_raster_ctx *c, int P, GeomScratch &scr, bool readback, hipStream_t stream, bool dbg) {
     if (!c->rect_mode) {
         DGS_HIP_CHECK(hipcub::DeviceScan::InclusiveSum(scr.p, scr.scan_bytes, c->tiles_sorted, c->offsets, P, stream));
         if (readback) {
@@ -614,7 +535,7 @@ static int count_pairs(dgs_raster_ctx *c, int P, GeomScratch &scr, uint32_t *max
     {
         ScopedTimer tm("count", stream);
         hipLaunchKernelGGL(k_rect_count, dim3(nb), dim3(256), 4ull * T, stream, P, c->tsort ? nullptr : c->order, c->xy,
-                           c->radii, c->gx, c->gy, c->rect_cnt, c->rect_total, maxtodo);
+                           c->radii, c->gx, c->gy, c->rect_cnt, c->rect_total);
     }
     DGS_LAUNCH_CHECK("k_rect_count", dbg, stream);
     {
@@ -635,7 +556,7 @@ static void ctx_release(dgs_raster_ctx *c) {
         g_pool.push_back(c);
     } else {
         c->geom.release(); c->bin.release(); c->img.release(); c->acc.release(); c->rect.release();
-        c->rtot.release(); c->ckb.release(); c->segq.release(); c->det.release();
+        c->rtot.release(); c->det.release();
         if (c->h_total) (void)hipHostFree(c->h_total);
         delete c;
     }
@@ -715,12 +636,6 @@ static int raster_forward(const dgs_raster_settings *s, int P, int M, const floa
     c->n_contrib = (uint32_t *)(im + off_n);
     if (int rc = carve_rect(c, P, stream)) return rc;
     c->det_fwd = c->rect_mode && g_det.get();
-    c->seg_ok = c->rect_mode && g_blend_seg.get();
-    if (c->seg_ok) {
-        const size_t cap0 = c->segq.cap;
-        if (int rc = c->segq.ensure(4ull * (T + 4))) return rc;
-        if (c->segq.cap != cap0) DGS_HIP_CHECK(hipMemsetAsync(c->segq.p, 0, c->segq.cap, stream));
-    }
 
     const float fx = c->W / (2.f * s->tanfovx), fy = c->H / (2.f * s->tanfovy);
     int nr = 0;
@@ -739,21 +654,21 @@ static int raster_forward(const dgs_raster_settings *s, int P, int M, const floa
                                out_visible);
         }
         DGS_LAUNCH_CHECK("k_preprocess", dbg, stream);
-        if (int rc = depth_order(c, P, scr, stream, dbg)) return rc;
+        if (int rc = depth_order(c, P, stream, dbg)) return rc;
         if (!c->h_total) {  // coherent + mapped: k_rect_colscan stores the count into it directly
             DGS_HIP_CHECK(hipHostMalloc((void **)&c->h_total, sizeof(uint32_t), hipHostMallocCoherent | hipHostMallocMapped));
             DGS_HIP_CHECK(hipHostGetDevicePointer((void **)&c->d_total, c->h_total, 0));
         }
         if (!c->count_ev) DGS_HIP_CHECK(hipEventCreateWithFlags(&c->count_ev, hipEventDisableTiming));
         if (c->rect_mode) *(volatile uint32_t *)c->h_total = COUNT_PENDING;  // k_rect_colscan overwrites it
-        if (int rc = count_pairs(c, P, scr, c->seg_ok ? (uint32_t *)c->segq.p + 2 : nullptr, true, stream, dbg)) return rc;
+        if (int rc = count_pairs(c, P, scr, true, stream, dbg)) return rc;
         int cap = pair_cap_get(device);
         const bool speculative = cap > 0 && !dbg;
         if (!speculative) {
             if (int rc = wait_count(c, stream, nr)) return rc;
             cap = nr;
         }
-        if (int rc = bin_and_blend(c, cap, P, device, stream, dbg, out_color, out_depth)) return rc;
+        if (int rc = bin_and_blend(c, cap, P, stream, dbg, out_color, out_depth)) return rc;
         if (speculative && g_deferred.load()) {  // num_rendered read by the backward (resolve_count)
             c->count_pending = true;
             c->spec_cap = cap;
@@ -770,12 +685,12 @@ static int raster_forward(const dgs_raster_settings *s, int P, int M, const floa
                     std::lock_guard<std::mutex> lk(g_cap_mu);
                     g_redos++;
                 }
-                if (int rc = bin_and_blend(c, nr, P, device, stream, dbg, out_color, out_depth)) return rc;
+                if (int rc = bin_and_blend(c, nr, P, stream, dbg, out_color, out_depth)) return rc;
             }
         }
         pair_cap_observe(device, nr);
     } else {
-        if (int rc = bin_and_blend(c, 0, P, device, stream, dbg, out_color, out_depth)) return rc;
+        if (int rc = bin_and_blend(c, 0, P, stream, dbg, out_color, out_depth)) return rc;
     }
     c->num_rendered = nr;
     guard.c = nullptr;
@@ -849,22 +764,10 @@ static int raster_backward(dgs_raster_ctx *c, const float *dL_dcolor, const floa
                            cap, (const float4 *)slot, acc, (int)stage);
     } else if (cap > 0) {
         ScopedTimer tm("blend_bwd", stream);
-        if (c->seg_ok && !dL_ddepth) {
-            static int cus = 0;
-            if (!cus) DGS_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-            uint32_t *q = (uint32_t *)c->segq.p;
-            hipLaunchKernelGGL(k_blend_bwd2s, dim3(cus * BWD_SEG_WGS_PER_CU), dim3(B2), 0, stream, c->ranges, c->vals, cap,
-                               c->W, c->H, c->gx, T, c->s.bg, c->xy, c->conic_o, c->rgbd, c->final_T, c->n_contrib,
-                               c->cfin, (const float4 *)c->ckb.p, q + 4, q + 2, q, dL_dcolor, acc);
-        } else
-            if (dL_ddepth)
-                hipLaunchKernelGGL((k_blend_bwd2<true, false>), dim3(T), dim3(B2), 0, stream, c->ranges, c->vals, cap, c->W,
-                                   c->H, c->gx, c->s.bg, c->xy, c->conic_o, c->rgbd, c->final_T, c->n_contrib, dL_dcolor,
-                                   dL_ddepth, acc, nullptr, nullptr, nullptr);
-            else
-                hipLaunchKernelGGL((k_blend_bwd2<false, false>), dim3(T), dim3(B2), 0, stream, c->ranges, c->vals, cap, c->W,
-                                   c->H, c->gx, c->s.bg, c->xy, c->conic_o, c->rgbd, c->final_T, c->n_contrib, dL_dcolor,
-                                   nullptr, acc, nullptr, nullptr, nullptr);
+        hipLaunchKernelGGL((dL_ddepth ? k_blend_bwd2<true, false> : k_blend_bwd2<false, false>), dim3(T), dim3(B2), 0,
+                           stream, c->ranges, c->vals, cap, c->W, c->H, c->gx, c->s.bg, c->xy, c->conic_o, c->rgbd,
+                           c->final_T, c->n_contrib, dL_dcolor, dL_ddepth, acc, (float *)nullptr, (uint32_t *)nullptr,
+                           (const uint32_t *)nullptr);
     }
     DGS_LAUNCH_CHECK("k_blend_bwd2", dbg, stream);
     const float fx = c->W / (2.f * c->s.tanfovx), fy = c->H / (2.f * c->s.tanfovy);
@@ -954,14 +857,10 @@ extern "C" void dgs_debug_set_pair_cap(int device, int cap) {
 
 extern "C" int dgs_debug_pair_cap(int device) { return pair_cap_get(device); }
 
-extern "C" void dgs_debug_set_blend_seg(int on) { g_blend_seg.set(on); }
 extern "C" void dgs_raster_set_deterministic(int on) { g_det.set(on); }
 extern "C" void dgs_debug_set_tile_sort(int on) { g_tile_sort.set(on); }
-extern "C" void dgs_debug_set_blend_fwd2(int on) { g_fwd2.set(on); }
-extern "C" int dgs_debug_get_blend_fwd2(void) { return g_fwd2.get() ? 1 : 0; }
 extern "C" int dgs_debug_get_tile_sort(void) { return g_tile_sort.get() ? 1 : 0; }
 extern "C" int dgs_raster_get_deterministic(void) { return g_det.get() ? 1 : 0; }
-extern "C" int dgs_debug_get_blend_seg(void) { return g_blend_seg.get() ? 1 : 0; }
 
 extern "C" void dgs_debug_set_binning(int mode) { g_sort_binning.set(mode == 1); }
 
@@ -980,7 +879,7 @@ extern "C" long long dgs_debug_binning_redos(void) {
 // ================================================================================================
 // The workspace reuses dgs_raster_ctx as the container of the geometry / binning buffers and their carved
 // views (so bin_lists and the count wait are the training forward's own), but it never enters the
-// context pool and nothing of the backward's lives in it: acc, ckb, segq, det stay unallocated, img
+// context pool and nothing of the backward's lives in it: acc and det stay unallocated, img
 // holds the tile ranges only, clamped / final_T / n_contrib are null.
 namespace dgs {
 struct RenderWs {
@@ -1109,7 +1008,6 @@ int render_raster_frame(RenderWs *ws, const RenderRasterIn &in, int f, int known
     c->n_contrib = nullptr;
     if (int rc = carve_rect(c, P, stream)) return rc;
     c->det_fwd = false;
-    c->seg_ok = false;
     if (redo && in.depth8) DGS_HIP_CHECK(hipMemsetAsync(ws->dmax + f, 0, 4, stream));
     int cap = 0;
     if (P > 0) {
@@ -1124,11 +1022,11 @@ int render_raster_frame(RenderWs *ws, const RenderRasterIn &in, int f, int known
                                (uint8_t *)nullptr);
         }
         DGS_LAUNCH_CHECK("k_preprocess", false, stream);
-        if (int rc = depth_order(c, P, scr, stream, false)) return rc;
+        if (int rc = depth_order(c, P, stream, false)) return rc;
         // the frame's pair count: its own host word (a redo already knows it: the device-side dummy word)
         c->h_total = ws->h_counts + f;
         c->d_total = redo ? ws->dummy : ws->d_counts + f;
-        if (int rc = count_pairs(c, P, scr, nullptr, !redo, stream, false)) return rc;
+        if (int rc = count_pairs(c, P, scr, !redo, stream, false)) return rc;
         if (!redo) ws->last = f;
         cap = redo ? known_count : pair_cap_get(device);
         if (!redo && cap <= 0) {  // no learned capacity: this frame waits for its own count, as the forward does
@@ -1140,7 +1038,7 @@ int render_raster_frame(RenderWs *ws, const RenderRasterIn &in, int f, int known
         }
     }
     ws->caps[(size_t)f] = cap;
-    if (int rc = bin_lists(c, cap, P, device, stream, false)) return rc;
+    if (int rc = bin_lists(c, cap, P, stream, false)) return rc;
     const bool want8 = in.depth8 != nullptr;
     float *depth = in.depth ? in.depth : (want8 ? ws->depth_scratch : nullptr);
     const int pack_rgb = in.rgb8 && c->W % 4 == 0 && (reinterpret_cast<uintptr_t>(in.rgb8) & 3) == 0;

@@ -6,8 +6,8 @@
 //   k_rect_place     every block writes its Gaussians' ids into its slice of each tile's list
 //   k_tile_sort      per-tile stable sort of the list by depth key (LDS; global scratch for long lists)
 //   k_rect_gather    DGS_DETERMINISTIC=1: sums the blend backward's per-pair slots in k_rect_place's order
-//   k_gather_tiles, k_duplicate, k_ranges   DGS_BINNING=sort: (tile, id) pairs in global depth order for
-//                    the stable radix sort on the tile bits, then the ranges
+//   k_duplicate, k_ranges   DGS_BINNING=sort: (tile, id) pairs in global depth order for the stable radix
+//                    sort on the tile bits, then the ranges
 //   k_clip_ranges    a deferred pair count that overflowed: the ranges clipped to the launched capacity
 #pragma once
 #include "raster_kernels.h"
@@ -17,13 +17,6 @@ namespace dgs {
 // Pairs are emitted in depth order (Gaussians pre-sorted by depth, stable on the index), so a
 // stable sort on the tile id alone yields the reference's (tile, depth) key order, ties on the
 // Gaussian index included: 2 radix passes over 16-bit keys instead of 6 over 64-bit ones.
-__global__ __launch_bounds__(256) void k_gather_tiles(int P, const uint32_t *__restrict__ order,
-                                                      const uint32_t *__restrict__ tiles,
-                                                      uint32_t *__restrict__ tiles_sorted) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < P) tiles_sorted[j] = tiles[order[j]];
-}
-
 template <class KT>
 __global__ __launch_bounds__(256) void k_duplicate(int P, const uint32_t *__restrict__ order,
                                                    const float2 *__restrict__ xy, const int *__restrict__ radii,
@@ -78,13 +71,11 @@ __device__ inline bool gauss_rect(uint32_t g, const float2 *xy, const int *radii
 
 __global__ __launch_bounds__(256) void k_rect_count(int P, const uint32_t *__restrict__ order, const float2 *__restrict__ xy,
                                                     const int *__restrict__ radii, int gx, int gy,
-                                                    uint32_t *__restrict__ cnt, uint32_t *__restrict__ total,
-                                                    uint32_t *__restrict__ maxtodo) {
+                                                    uint32_t *__restrict__ cnt, uint32_t *__restrict__ total) {
     extern __shared__ uint32_t h[];  // [T]  (total[0] = pair count, total[1] = column-scan ticket)
     const int T = gx * gy;
     for (int t = threadIdx.x; t < T; t += 256) h[t] = 0;
     if (blockIdx.x == 0 && threadIdx.x < 2) total[threadIdx.x] = 0;  // k_rect_colscan adds into them
-    if (maxtodo && blockIdx.x == 0 && threadIdx.x == 0) *maxtodo = 0;  // k_blend_fwd maxes into it
     __syncthreads();
     const int j = blockIdx.x * 256 + threadIdx.x;
     int4 rc;

@@ -1,18 +1,15 @@
 // Rasterizer, blend stage (device code of raster.hip's translation unit; the pipeline map is at the top of
 // raster.hip). Every kernel here runs one workgroup per 16x16 tile over the tile's depth-ordered list:
 //   k_blend_fwd      1 workgroup (4 waves) / 16x16 tile, LDS-staged 256-Gaussian batches, block-wide
-//                    early exit; writes colour, depth, final T, last contributor (<true>: and the
-//                    segmented backward's checkpoints)
+//                    early exit; writes colour, depth, final T, last contributor
 //   k_blend_img      the forward-only blend of dgs_render_frames (+ k_depth8): same staging and step
-//   k_blend_fwd2     DGS_BLEND_FWD2=1: the two-pixels-per-lane forward blend
 //   k_blend_bwd2     back-to-front replay from the block's max contributor, two pixels per lane; the 12
 //                    per-Gaussian gradient sums reduced across the wave and added with float atomics
 //                    (<.., true>, DGS_DETERMINISTIC=1: left in per-pair slots for k_rect_gather)
-//   k_blend_bwd2s    DGS_BLEND_SEG=1: segmented blend backward from k_blend_fwd<true>'s checkpoints
 // The backward replays the forward's alphas bit for bit, so what the kernels share is stated once:
 //   the cull (tile_reach), the alpha evaluation (conic_q, q_power, q_alpha)
-//   stage_fwd<NT, TRACK>   the forward's staging round (all three forward kernels)
-//   blend_step<TRACK>      the forward's per-(pixel, Gaussian) step; k_blend_fwd2 holds its packed form
+//   stage_fwd<TRACK>       the forward's staging round (both forward kernels)
+//   blend_step<TRACK>      the forward's per-(pixel, Gaussian) step
 //   pair_alpha, pair_load, pair_grad<DEPTH>, lane_scale, row_add   the backward's pixel-pair pieces
 #pragma once
 #include "raster_kernels.h"
@@ -63,7 +60,7 @@ __device__ __forceinline__ float q_alpha(const float4 &q, float G) { return fmin
 // staged per round (k_blend_fwd, k_blend_img). Two pixels per lane: B2 threads (2 waves), wave w covering
 // the 16x8 half (rows 8w..8w+7), lane l the pixel pair (l & 7, row) and (8 + (l & 7), row): one dy, a
 // packed dx, the per-(pixel, Gaussian) arithmetic as packed fp32 (v_pk_fma_f32 / v_pk_mul_f32 /
-// v_pk_add_f32); B2 Gaussians staged per round (k_blend_fwd2, k_blend_bwd2, k_blend_bwd2s).
+// v_pk_add_f32); B2 Gaussians staged per round (k_blend_bwd2).
 typedef float f2 __attribute__((ext_vector_type(2)));
 constexpr int B2 = 128;
 __device__ __forceinline__ f2 sel2(bool a, bool b, f2 x, f2 y) { return f2{a ? x.x : y.x, b ? x.y : y.y}; }
@@ -152,34 +149,23 @@ __device__ __forceinline__ TilePix2 tile_front2(int tile, int lane, int wv, int 
     return t;
 }
 
-// Segmented blend backward (k_blend_bwd2s): the forward leaves, every SEG list positions of a tile,
-// each pixel's (T, C) before that position (a "checkpoint", state before the Gaussians from there on),
-// and the tile's backward work (the largest last-contributor position + 1); the backward then runs
-// every SEG-long segment of every tile as an independent work item (segment-major), starting from the
-// checkpoint at the segment's end instead of replaying the whole list from the end.
-constexpr int SEG = 128;
-// checkpoint slot of list position gp (absolute, gp = tile start + a multiple of SEG, strictly inside the
-// tile's list): gp / SEG is unique across tiles (the next tile's first boundary lies >= SEG past every
-// boundary of this one)
-__device__ __forceinline__ uint32_t ckpt_slot(uint32_t gp) { return gp / SEG; }
-
 // ------------------------------------------------------------------------------------------------
-// The forward blend core: one staging round and one per-(pixel, Gaussian) step, shared by k_blend_fwd,
-// k_blend_img and (the staging) k_blend_fwd2. The cull, the alpha evaluation and the predicates are
-// changed here, once; the kernels keep their loops, exits and bookkeeping.
+// The forward blend core: one staging round and one per-(pixel, Gaussian) step, shared by k_blend_fwd
+// and k_blend_img. The cull, the alpha evaluation and the predicates are changed here, once; the
+// kernels keep their loops, exits and bookkeeping.
 // ------------------------------------------------------------------------------------------------
-// Staging round r of NT threads over the tile's list: positions [NT r, NT (r + 1)) are loaded, culled
-// against the tile (tile_reach) and compacted into s_xy / s_co (exponent form) / s_cd, with s_pos (TRACK)
-// each kept entry's position in the list. The batch is padded to a multiple of 4 with inert entries (zero
-// conic and opacity: power 0, alpha 0, never used), so the blend loop tests for its early exit once per 4
-// Gaussians. Returns the padded count; the barrier behind the stores is taken, and s_wcnt holds the waves'
-// kept counts.
-template <int NT, bool TRACK>
+// Staging round r of the workgroup's TILE_PIX threads over the tile's list: positions [TILE_PIX r,
+// TILE_PIX (r + 1)) are loaded, culled against the tile (tile_reach) and compacted into s_xy / s_co
+// (exponent form) / s_cd, with s_pos (TRACK) each kept entry's position in the list. The batch is padded to
+// a multiple of 4 with inert entries (zero conic and opacity: power 0, alpha 0, never used), so the blend
+// loop tests for its early exit once per 4 Gaussians. Returns the padded count; the barrier behind the
+// stores is taken.
+template <bool TRACK>
 __device__ __forceinline__ int stage_fwd(int r, int tid, uint2 range, float tx0, float ty0,
                                          const uint32_t *__restrict__ vals, const float2 *__restrict__ xy,
                                          const float4 *__restrict__ conic_o, const float4 *__restrict__ rgbd,
                                          float2 *s_xy, float4 *s_co, float4 *s_cd, int *s_pos, uint32_t *s_wcnt) {
-    const int prog = r * NT + tid;
+    const int prog = r * TILE_PIX + tid;
     bool keep = false;
     uint32_t id = 0;
     float2 gl;
@@ -190,7 +176,7 @@ __device__ __forceinline__ int stage_fwd(int r, int tid, uint2 range, float tx0,
         cl = conic_o[id];
         keep = tile_reach(gl, cl, tx0, ty0);
     }
-    const int2 sl = compact_slot_n<NT / 64>(keep, tid, s_wcnt);
+    const int2 sl = compact_slot_n<TILE_PIX / 64>(keep, tid, s_wcnt);
     if (keep) {
         s_xy[sl.x] = gl;
         s_co[sl.x] = conic_q(cl);
@@ -255,15 +241,12 @@ __device__ __forceinline__ PairAlpha pair_alpha(float mx, float my, const float4
     return a;
 }
 
-template <bool CK>  // CK: write the segmented backward's checkpoints, final state and per-tile work
 __global__ __launch_bounds__(256) void k_blend_fwd(const uint2 *__restrict__ ranges, const uint32_t *__restrict__ vals,
                                                    uint32_t cap, int W, int H, int gx, const float2 *__restrict__ xy,
                                                    const float4 *__restrict__ conic_o, const float4 *__restrict__ rgbd,
                                                    const float *bg, float *__restrict__ final_T,
                                                    uint32_t *__restrict__ n_contrib, float *__restrict__ out_color,
-                                                   float *__restrict__ out_depth, float4 *__restrict__ ckpt,
-                                                   uint32_t *__restrict__ tile_todo, uint32_t *__restrict__ maxtodo,
-                                                   float4 *__restrict__ cfin) {
+                                                   float *__restrict__ out_depth) {
     __shared__ float2 s_xy[TILE_PIX];
     __shared__ float4 s_co[TILE_PIX];
     __shared__ float4 s_cd[TILE_PIX];
@@ -272,36 +255,20 @@ __global__ __launch_bounds__(256) void k_blend_fwd(const uint2 *__restrict__ ran
     const int tile = blockIdx.x;
     const int tid = threadIdx.x;
     const TilePix t = tile_front(tile, tid, gx, W, H, ranges, cap);
-    const int todo_total = (int)(t.range.y - t.range.x);
-    const int rounds = div_up(todo_total, TILE_PIX);
+    const int rounds = div_up((int)(t.range.y - t.range.x), TILE_PIX);
     BlendPix p;
     bool done = !t.inside;
     uint32_t last = 0;
     for (int r = 0; r < rounds; r++) {
         if (__syncthreads_count(done) == TILE_PIX) break;
-        const int n4 = stage_fwd<TILE_PIX, true>(r, tid, t.range, (float)t.tx0, (float)t.ty0, vals, xy, conic_o, rgbd,
-                                                 s_xy, s_co, s_cd, s_pos, s_wcnt);
-        // checkpoints (segmented backward): the state before positions 256 r + 128 and 256 (r + 1); the
-        // first half of the batch (threads 0..127 = waves 0, 1) staged jmid kept Gaussians
-        const int jmid = CK ? (int)(s_wcnt[0] + s_wcnt[1]) : -1;
-        const uint32_t pix = (uint32_t)(t.tp.y * TILE_X + t.tp.x);
-        auto put_ckpt = [&](int lp) {  // lp: position in the tile's list (a multiple of SEG, > 0)
-            if (CK && t.inside && lp < todo_total)
-                ckpt[(size_t)ckpt_slot(t.range.x + (uint32_t)lp) * TILE_PIX + pix] = make_float4(p.T, p.C0, p.C1, p.C2);
-        };
-        bool mid_done = false;
+        const int n4 = stage_fwd<true>(r, tid, t.range, (float)t.tx0, (float)t.ty0, vals, xy, conic_o, rgbd, s_xy, s_co,
+                                       s_cd, s_pos, s_wcnt);
         p.lastj = 0;
         for (int j0 = 0; j0 < n4; j0 += 4) {
             if (__ballot(!done) == 0ull) break;
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 const int j = j0 + u;
-                if constexpr (CK) {
-                    if (j == jmid) {
-                        put_ckpt(r * TILE_PIX + SEG);
-                        mid_done = true;
-                    }
-                }
                 const float2 g = s_xy[j];
                 const float4 q = s_co[j];
                 const float4 cd = s_cd[j];
@@ -309,25 +276,9 @@ __global__ __launch_bounds__(256) void k_blend_fwd(const uint2 *__restrict__ ran
             }
         }
         if (p.lastj) last = (uint32_t)s_pos[p.lastj - 1] + 1u;  // list position + 1 (n_contrib of the full list)
-        if constexpr (CK) {  // (a wave that left the batch early: its pixels are done, their state is final)
-            if (!mid_done) put_ckpt(r * TILE_PIX + SEG);
-            put_ckpt((r + 1) * TILE_PIX);
-        }
-    }
-    if constexpr (CK) {  // the tile's backward work: the largest last-contributor position + 1
-        __shared__ uint32_t s_todo;
-        if (tid == 0) s_todo = 0;
-        __syncthreads();
-        if (t.inside) atomicMax(&s_todo, last);
-        __syncthreads();
-        if (tid == 0) {
-            tile_todo[tile] = s_todo;
-            atomicMax(maxtodo, s_todo);
-        }
     }
     if (t.inside) {
         int pid = t.py * W + t.px;
-        if constexpr (CK) cfin[pid] = make_float4(p.T, p.C0, p.C1, p.C2);  // the final state (segmented backward)
         final_T[pid] = p.T;
         n_contrib[pid] = last;
         int HW = H * W;
@@ -338,7 +289,7 @@ __global__ __launch_bounds__(256) void k_blend_fwd(const uint2 *__restrict__ ran
     }
 }
 
-// Forward-only blend (dgs_render_frames): k_blend_fwd<false>'s staging round and per-pixel step (stage_fwd,
+// Forward-only blend (dgs_render_frames): k_blend_fwd's staging round and per-pixel step (stage_fwd,
 // blend_step, above), so T, C and depth are bitwise its values; what differs is the bookkeeping
 // (TRACK = false). No last-contributor tracking (no s_pos in LDS, no per-batch map), no final_T / n_contrib, and
 // the epilogue writes only what the caller asked for, from registers: float CHW colour / depth, 1 - T, the
@@ -371,8 +322,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k
     bool done = !t.inside;
     for (int r = 0; r < rounds; r++) {
         if (__syncthreads_count(done) == TILE_PIX) break;
-        const int n4 = stage_fwd<TILE_PIX, false>(r, tid, t.range, (float)t.tx0, (float)t.ty0, vals, xy, conic_o, rgbd,
-                                                  s_xy, s_co, s_cd, nullptr, s_wcnt);
+        const int n4 = stage_fwd<false>(r, tid, t.range, (float)t.tx0, (float)t.ty0, vals, xy, conic_o, rgbd, s_xy, s_co,
+                                        s_cd, nullptr, s_wcnt);
         for (int j0 = 0; j0 < n4; j0 += 4) {
             if (__ballot(!done) == 0ull) break;
 #pragma unroll
@@ -448,83 +399,6 @@ __global__ __launch_bounds__(256) void k_depth8(int HW, const float *__restrict_
     for (int j = i; j < min(i + 4, HW); j++) out[j] = (uint8_t)to8b(depth[j] / den);
 }
 
-// Forward blend, two pixels per lane (DGS_BLEND_FWD2=1; the segmented backward's checkpoints stay on
-// k_blend_fwd): the pixel-pair layout with B2-Gaussian batches (stage_fwd), so every staged Gaussian's
-// broadcast LDS reads serve two pixels and the per-pixel arithmetic runs on packed fp32 pairs: blend_step
-// in packed form. Per pixel the operations, their order and the fused forms are blend_step's: the image,
-// the transmittance and n_contrib are bitwise the same (GPU test).
-__global__ __launch_bounds__(B2) void k_blend_fwd2(const uint2 *__restrict__ ranges, const uint32_t *__restrict__ vals,
-                                                   uint32_t cap, int W, int H, int gx, const float2 *__restrict__ xy,
-                                                   const float4 *__restrict__ conic_o, const float4 *__restrict__ rgbd,
-                                                   const float *bg, float *__restrict__ final_T,
-                                                   uint32_t *__restrict__ n_contrib, float *__restrict__ out_color,
-                                                   float *__restrict__ out_depth) {
-    __shared__ float2 s_xy[B2];
-    __shared__ float4 s_co[B2];
-    __shared__ float4 s_cd[B2];
-    __shared__ int s_pos[B2];
-    __shared__ uint32_t s_wcnt[B2 / 64];
-    const int tile = blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const TilePix2 t = tile_front2(tile, lane, wv, gx, W, H, ranges, cap);
-    const int px0 = t.px0, px1 = t.px1, py = t.py;
-    const bool in0 = t.in0, in1 = t.in1;
-    const int rounds = div_up((int)(t.range.y - t.range.x), B2);
-    bool done0 = !in0, done1 = !in1;
-    const f2 zero = f2{0.f, 0.f};
-    f2 T = f2{1.f, 1.f}, C0 = zero, C1 = zero, C2 = zero, Dd = zero;
-    uint32_t last0 = 0, last1 = 0;
-    for (int r = 0; r < rounds; r++) {
-        if (__syncthreads_count(done0 && done1) == B2) break;
-        const int n4 = stage_fwd<B2, true>(r, tid, t.range, (float)t.tx0, (float)t.ty0, vals, xy, conic_o, rgbd, s_xy,
-                                           s_co, s_cd, s_pos, s_wcnt);
-        int lastj0 = 0, lastj1 = 0;
-        for (int j0 = 0; j0 < n4; j0 += 4) {
-            if (__ballot(!(done0 && done1)) == 0ull) break;
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const int j = j0 + u;
-                const float2 g = s_xy[j];
-                const float4 q = s_co[j];
-                const float4 cd = s_cd[j];
-                const PairAlpha a = pair_alpha(g.x, g.y, q, t.pfx, t.pfy);
-                const f2 power = a.power, alpha = a.alpha;
-                const f2 testT = T * (1.f - alpha);
-                bool use0 = !done0 && !(power.x > 0.f) && !(alpha.x < 1.f / 255.f);
-                bool use1 = !done1 && !(power.y > 0.f) && !(alpha.y < 1.f / 255.f);
-                const bool stop0 = use0 && testT.x < 0.0001f, stop1 = use1 && testT.y < 0.0001f;
-                done0 = done0 || stop0;
-                done1 = done1 || stop1;
-                use0 = use0 && !stop0;
-                use1 = use1 && !stop1;
-                const f2 w = sel2(use0, use1, alpha * T, zero);
-                C0 += cd.x * w;
-                C1 += cd.y * w;
-                C2 += cd.z * w;
-                Dd += cd.w * w;
-                T = sel2(use0, use1, testT, T);
-                lastj0 = use0 ? j + 1 : lastj0;
-                lastj1 = use1 ? j + 1 : lastj1;
-            }
-        }
-        if (lastj0) last0 = (uint32_t)s_pos[lastj0 - 1] + 1u;  // list position + 1 (n_contrib of the full list)
-        if (lastj1) last1 = (uint32_t)s_pos[lastj1 - 1] + 1u;
-    }
-    const int HW = H * W;
-    auto put = [&](int px, float Tp, uint32_t last, float c0, float c1, float c2, float d) {
-        const int pid = py * W + px;
-        final_T[pid] = Tp;
-        n_contrib[pid] = last;
-        out_color[pid] = c0 + Tp * bg[0];
-        out_color[HW + pid] = c1 + Tp * bg[1];
-        out_color[2 * HW + pid] = c2 + Tp * bg[2];
-        out_depth[pid] = d;
-    };
-    if (in0) put(px0, T.x, last0, C0.x, C1.x, C2.x, Dd.x);
-    if (in1) put(px1, T.y, last1, C0.y, C1.y, C2.y, Dd.y);
-}
-
 // ------------------------------------------------------------------------------------------------
 // backward kernels
 // ------------------------------------------------------------------------------------------------
@@ -555,8 +429,7 @@ __device__ inline float row_sum15(float v) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// Blend backward, two pixels per lane (k_blend_bwd2, the default, and the segmented k_blend_bwd2s): the
-// pixel-pair layout, so the per-(pixel, Gaussian) arithmetic runs as packed fp32 (two pixels per
+// Blend backward, two pixels per lane (k_blend_bwd2): the pixel-pair layout, so the per-(pixel, Gaussian) arithmetic runs as packed fp32 (two pixels per
 // instruction), and the per-(wave, Gaussian) gradient reduction covers 128 pixels instead of 64 (half as
 // many reductions and atomics per Gaussian as with one pixel per lane, which measured 0.315-0.322 against
 // 0.283 ms at P = 1.0 M pairs). Per-pixel activity becomes selects: an inactive pixel of a pair keeps its
@@ -566,8 +439,8 @@ __device__ inline float row_sum15(float v) {
 // to pay for half the waves per tile.)
 // The shared pieces: pair_load (a pixel pair's inputs), lane_scale and row_add (the fields' constant
 // factors and the add of the reduced sums), and pair_grad, the per-(pixel pair, Gaussian) gradient with
-// its reduction: the one place to change a gradient term. The kernels keep their staging, their skip
-// test and where the sums go.
+// its reduction: the one place to change a gradient term. The kernel keeps its staging, its skip test
+// and where the sums go.
 // ------------------------------------------------------------------------------------------------
 struct PairIn {
     f2 Tfinal, dp0, dp1, dp2, ddep;  // final transmittance, dL/dcolour, dL/ddepth (DEPTH, else 0)
@@ -821,119 +694,6 @@ __global__ __launch_bounds__(B2) void k_blend_bwd2(const uint2 *__restrict__ ran
                 dst[2] = s_slot[3 * tid + 2];
             }
         }
-    }
-}
-
-// Segmented blend backward (no depth gradient: every training step). A persistent grid takes work items
-// (segment s, tile) in segment-major order from a queue; item (s, tile) replays list positions
-// [SEG s, min(SEG (s + 1), todo)) of the tile back to front, starting from the forward's checkpoint at
-// the segment's end: T = the transmittance before that position, and the colour behind it (acc) =
-// (C_final - C_before) / T. A long tile list thus runs as several concurrent work items instead of one
-// serial replay, and the grid is filled with ~2x the waves of k_blend_bwd2. The per-(pixel, Gaussian)
-// arithmetic and the reduction are k_blend_bwd2's (pair_grad); its skip test and its staging (the id in an
-// array of its own) are not. Numerics: acc's rounding error is ~1 ulp / T, but
-// it enters dL/dalpha multiplied by the Gaussian's own transmittance (<= T), so the gradient error stays
-// at the ulp level of dL/dpix.
-constexpr int BWD_SEG_WGS_PER_CU = 12;
-__global__ __launch_bounds__(B2) void k_blend_bwd2s(const uint2 *__restrict__ ranges, const uint32_t *__restrict__ vals,
-                                                   uint32_t cap, int W, int H, int gx, int T_tiles, const float *bg,
-                                                   const float2 *__restrict__ xy, const float4 *__restrict__ conic_o,
-                                                   const float4 *__restrict__ rgbd, const float *__restrict__ final_T,
-                                                   const uint32_t *__restrict__ n_contrib,
-                                                   const float4 *__restrict__ cfin, const float4 *__restrict__ ckpt,
-                                                   const uint32_t *__restrict__ tile_todo,
-                                                   const uint32_t *__restrict__ maxtodo, uint32_t *__restrict__ queue,
-                                                   const float *__restrict__ dL_dpix, float *__restrict__ acc) {
-    __shared__ float2 s_xy[B2];
-    __shared__ float4 s_co[B2];
-    __shared__ float4 s_q[B2];
-    __shared__ float4 s_cd[B2];
-    __shared__ uint32_t s_id[B2];
-    __shared__ int s_pos[B2];
-    __shared__ uint32_t s_wcnt[B2 / 64];
-    __shared__ int s_item;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const LaneScale sc = lane_scale(lane, W, H);
-    const f2 zero = f2{0.f, 0.f};
-    const int nitems = div_up((int)*maxtodo, SEG) * T_tiles;
-    for (;;) {
-        __syncthreads();  // the previous item's staged LDS and s_item are consumed
-        if (tid == 0) s_item = (int)atomicAdd(queue, 1u);
-        __syncthreads();
-        const int item = s_item;
-        if (item >= nitems) break;
-        const int seg = item / T_tiles, tile = item - seg * T_tiles;
-        const int todo = (int)tile_todo[tile];
-        const int a = seg * SEG;
-        if (a >= todo) continue;
-        const int bnd = min(a + SEG, todo);  // the segment [a, bnd) of the tile's list
-        const TilePix2 t = tile_front2(tile, lane, wv, gx, W, H, ranges, cap);
-        const PairIn in = pair_load<false>(t, W, H, bg, final_T, n_contrib, dL_dpix, nullptr);
-        // the state at the segment's end: the final one, or from the checkpoint there
-        PairState st = {in.Tfinal, zero, zero, zero, zero};
-        if (bnd != todo) {
-            const float4 *ck = ckpt + (size_t)ckpt_slot(t.range.x + (uint32_t)bnd) * TILE_PIX + t.ly * TILE_X + t.lx0;
-            st.T = f2{1.f, 1.f};
-            if (t.in0) {
-                const float4 c = ck[0], f = cfin[t.py * W + t.px0];
-                const float it = 1.f / c.x;
-                st.T.x = c.x;
-                st.acc0.x = (f.y - c.y) * it;
-                st.acc1.x = (f.z - c.z) * it;
-                st.acc2.x = (f.w - c.w) * it;
-            }
-            if (t.in1) {
-                const float4 c = ck[8], f = cfin[t.py * W + t.px1];
-                const float it = 1.f / c.x;
-                st.T.y = c.x;
-                st.acc0.y = (f.y - c.y) * it;
-                st.acc1.y = (f.z - c.z) * it;
-                st.acc2.y = (f.w - c.w) * it;
-            }
-        }
-        // stage the segment (<= SEG = B2 positions) back to front, tile-culled and compacted
-        const int len = bnd - a;
-        bool keep = false;
-        uint32_t id = 0;
-        float2 gl;
-        float4 cl;
-        if (tid < len) {
-            id = vals[t.range.x + bnd - 1 - tid];
-            gl = xy[id];
-            cl = conic_o[id];
-            keep = tile_reach(gl, cl, (float)t.tx0, (float)t.ty0);
-        }
-        const int2 sl = compact_slot_n<B2 / 64>(keep, tid, s_wcnt);
-        if (keep) {
-            s_id[sl.x] = id;
-            s_xy[sl.x] = gl;
-            s_co[sl.x] = cl;
-            s_q[sl.x] = conic_q(cl);
-            s_cd[sl.x] = rgbd[id];
-            s_pos[sl.x] = tid;
-        }
-        __syncthreads();
-        const int n = sl.y;
-        for (int j = 0; j < n; j++) {
-            const uint32_t contributor = (uint32_t)(bnd - 1 - s_pos[j]);  // position in the tile's list
-            const float2 g = s_xy[j];
-            const float4 q = s_q[j];
-            const PairAlpha pa = pair_alpha(g.x, g.y, q, t.pfx, t.pfy);
-            const bool act0 = t.in0 && contributor < in.last0 && pa.power.x <= 0.f && pa.alpha.x >= 1.f / 255.f;
-            const bool act1 = t.in1 && contributor < in.last1 && pa.power.y <= 0.f && pa.alpha.y >= 1.f / 255.f;
-            if (__ballot(act0 || act1) == 0ull) continue;  // wave-uniform
-            const float4 cd = s_cd[j];
-            const float4 co = s_co[j];
-            float w0, w1, w2;
-            pair_grad<false>(act0, act1, pa, cd, co, in, st, w0, w1, w2);
-            if ((lane & 15) == 15) row_add(acc + (size_t)s_id[j] * ACC_STRIDE, lane, sc, w0, w1, w2);
-        }
-    }
-    // the last workgroup to leave resets the queue for the next launch (every take has returned)
-    if (tid == 0 && atomicAdd(queue + 1, 1u) == gridDim.x - 1) {
-        atomicExch(queue, 0u);
-        atomicExch(queue + 1, 0u);
     }
 }
 

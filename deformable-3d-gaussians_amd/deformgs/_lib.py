@@ -86,14 +86,10 @@ _SIGS = {
     "dgs_debug_sort_pairs": ([P, P, P, P, I, I, I, P], I),
     "dgs_raster_deferred_overflows": ([], ctypes.c_longlong),
     "dgs_debug_set_binning": ([I], None),
-    "dgs_debug_set_blend_seg": ([I], None),
     "dgs_raster_set_deterministic": ([I], None),
     "dgs_raster_get_deterministic": ([], I),
     "dgs_debug_set_tile_sort": ([I], None),
     "dgs_debug_get_tile_sort": ([], I),
-    "dgs_debug_set_blend_fwd2": ([I], None),
-    "dgs_debug_get_blend_fwd2": ([], I),
-    "dgs_debug_get_blend_seg": ([], I),
     "dgs_mlp_set_reserved_cus": ([I], None),
     "dgs_mlp_reserved_cus": ([], I),
     "dgs_debug_collective_standin": ([P, ctypes.c_longlong, I, I, P], I),

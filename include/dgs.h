@@ -134,13 +134,6 @@ void dgs_debug_set_pair_cap(int device, int cap);
 int dgs_debug_pair_cap(int device);
 void dgs_debug_set_binning(int mode);
 long long dgs_debug_binning_redos(void);
-/* Blend backward scheme (rect binning, no depth gradient): 1 = segmented (k_blend_bwd2s: every 128 list
- * positions of a tile an independent work item, started from per-pixel checkpoints the forward writes);
- * 0 = one serial back-to-front replay per tile (k_blend_bwd2). Default from DGS_BLEND_SEG. Applies to
- * forwards issued after the call. */
-void dgs_debug_set_blend_seg(int on);
-/* The blend-backward mode in effect (DGS_BLEND_SEG or the last dgs_debug_set_blend_seg): 1 = segmented. */
-int dgs_debug_get_blend_seg(void);
 /* Deterministic blend backward (rect binning): 1 = every (tile, Gaussian) pair's gradient terms are written
  * to per-pair slots and summed per Gaussian in a fixed order (k_rect_gather) instead of float atomics, so
  * repeated backwards of the same forward give bitwise-identical gradients (the upstream renderCUDA backward's
@@ -156,11 +149,6 @@ int dgs_raster_get_deterministic(void);
  * issued after the call. */
 void dgs_debug_set_tile_sort(int on);
 int dgs_debug_get_tile_sort(void);
-/* Forward blend with two pixels per lane (k_blend_fwd2; DGS_BLEND_FWD2=1): 1 = on. Images, transmittance and
- * per-pixel contributor counts are bitwise those of the default k_blend_fwd. Applies to forwards issued
- * after the call (not with the segmented backward's checkpoints). */
-void dgs_debug_set_blend_fwd2(int on);
-int dgs_debug_get_blend_fwd2(void);
 /* host nanoseconds spent waiting for num_rendered (and the number of waits) since process start */
 long long dgs_debug_count_wait_ns(long long *waits);
 /* dL/dscales convention. 0 (default) = the upstream CUDA op's: the gradient w.r.t. the modified scale

@@ -138,7 +138,7 @@ def test_sort_binning_path():
     gm, deform, cams, bg, six, color, depth, nr = _case("sh3")
     dev = torch.cuda.current_device()
     before = lib.dgs_debug_pair_cap(dev)
-    default = 1 if (os.environ.get("DGS_BINNING") == "sort" or os.environ.get("DGS_HIPCUB_SORT") == "1") else 0
+    default = 1 if os.environ.get("DGS_BINNING") == "sort" else 0
     try:
         lib.dgs_debug_set_binning(1)
         a = render_frames(cams, gm, deform, bg, outputs=("color", "depth"))
@@ -170,7 +170,7 @@ def test_shared_stages_both_callers(binning, tile_sort):
     gm, deform = S.gaussians(n=300), S.network()
     cams = S.cameras(2, width=48, height=40)
     bg = torch.zeros(3, device="cuda")
-    default = 1 if (os.environ.get("DGS_BINNING") == "sort" or os.environ.get("DGS_HIPCUB_SORT") == "1") else 0
+    default = 1 if os.environ.get("DGS_BINNING") == "sort" else 0
     ts_before = lib.dgs_debug_get_tile_sort()
     try:
         lib.dgs_debug_set_binning(1 if binning == "sort" else 0)

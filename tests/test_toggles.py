@@ -10,18 +10,14 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "deformable-3d-gaussians_amd")
-VARS = ("DGS_TILE_SORT", "DGS_BLEND_FWD2", "DGS_BLEND_SEG", "DGS_DETERMINISTIC")
-GETTERS = {"tile_sort": "dgs_debug_get_tile_sort", "fwd2": "dgs_debug_get_blend_fwd2",
-           "seg": "dgs_debug_get_blend_seg", "det": "dgs_raster_get_deterministic"}
+VARS = ("DGS_TILE_SORT", "DGS_DETERMINISTIC")
+GETTERS = {"tile_sort": "dgs_debug_get_tile_sort", "det": "dgs_raster_get_deterministic"}
 
 CASES = {
     # name: (environment, calls before the getters are printed, expected getter values)
-    "unset": ({}, "", {"tile_sort": 1, "fwd2": 0, "seg": 0, "det": 0}),
+    "unset": ({}, "", {"tile_sort": 1, "det": 0}),
     "tile_sort=0": ({"DGS_TILE_SORT": "0"}, "", {"tile_sort": 0}),
     "tile_sort=1": ({"DGS_TILE_SORT": "1"}, "", {"tile_sort": 1}),
-    "fwd2=1": ({"DGS_BLEND_FWD2": "1"}, "", {"fwd2": 1}),
-    "fwd2=0": ({"DGS_BLEND_FWD2": "0"}, "", {"fwd2": 0}),
-    "seg=1": ({"DGS_BLEND_SEG": "1"}, "", {"seg": 1}),
     "det=1": ({"DGS_DETERMINISTIC": "1"}, "", {"det": 1}),
     "set_before_read": ({"DGS_TILE_SORT": "0"}, "lib.dgs_debug_set_tile_sort(1)", {"tile_sort": 1}),
     "set_after_read": ({"DGS_TILE_SORT": "0"}, "assert lib.dgs_debug_get_tile_sort() == 0; lib.dgs_debug_set_tile_sort(1)",

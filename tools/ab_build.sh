@@ -1,9 +1,13 @@
 #!/bin/bash
-# Baseline library for A/B timing: source file $SRC (default raster) taken from git revision $REV
-# (default HEAD) and linked with the other current product objects -> lib/diag/libdgs_base.so
+# Baseline library for A/B timing: source file $SRC (default raster) with the headers beside it, all taken
+# from git revision $REV (default HEAD), linked with the other current product objects
+# -> lib/diag/libdgs_base.so
 set -eu
 cd "$(dirname "$0")/.."
 SRC=${SRC:-raster}; REV=${REV:-HEAD}
-git show $REV:deformable-3d-gaussians_amd/csrc/$SRC.hip > deformable-3d-gaussians_amd/csrc/${SRC}_abbase.hip
-EXCL=$SRC SRC=${SRC}_abbase bash tools/build_diag.sh base= || true
-rm -f deformable-3d-gaussians_amd/csrc/${SRC}_abbase.hip
+PKG=deformable-3d-gaussians_amd
+rm -rf $PKG/build_obj/abbase
+mkdir -p $PKG/build_obj/abbase
+git archive $REV $PKG/csrc include | tar -x -C $PKG/build_obj/abbase
+SRC=$SRC SRCDIR=build_obj/abbase/$PKG/csrc bash tools/build_diag.sh base=
+rm -rf $PKG/build_obj/abbase

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Alternating bench runs: product defaults vs the same library with an environment switch.
-#   ENVAB="DGS_BLEND_SEG=1" [RUNS=3] [TIMING=major] tools/env_ab.sh
+#   ENVAB="DGS_TILE_SORT=0" [RUNS=3] [TIMING=major] tools/env_ab.sh
 set -u
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out

@@ -3,7 +3,7 @@
 # its CPU baseline), config-sized bench lines, and a rocprofv3 kernel trace + stats plus the FETCH_SIZE /
 # WRITE_SIZE passes (tools/gpu_prof.sh). Every GPU step has its own time limit; a step that times out,
 # aborts or faults ends the session (a failing test does not). Outputs: gpurun_out/$TAG/.
-#   usage: TAG=r4b [PARTS="tests smoke bench configs prof ab stall tests:<file>,..."] tools/evidence.sh
+#   usage: TAG=r4b [PARTS="tests smoke bench configs prof stall outlier tests:<file>,..."] tools/evidence.sh
 set -u
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp PYTHONUNBUFFERED=1
@@ -32,11 +32,6 @@ for p in $PARTS; do
       log=$O/tests_$(echo "${p#tests:}" | tr ',' '_' | cut -c1-60).txt
       run 1000 $log python -u -m pytest $files -v --timeout 600 --timeout-method thread
       tail -3 $log ;;
-    ab)  # the segmented blend backward against the serial replay, kernel timings on
-      for s in 0 1; do
-        DGS_BLEND_SEG=$s run 200 $O/ab_seg$s.jsonl python bench.py --no-cpu-baseline --kernel-timing major
-        tail -1 $O/ab_seg$s.jsonl | cut -c1-200
-      done ;;
     smoke)
       run 300 $O/smoke.txt python -c "import __graft_entry__ as g; g.smoke()"
       tail -1 $O/smoke.txt ;;
@@ -49,13 +44,11 @@ for p in $PARTS; do
         run 300 $O/cfg.log python bench.py --no-cpu-baseline $a && tail -1 $O/cfg.log >> $O/configs.jsonl
       done
       cut -c1-160 $O/configs.jsonl ;;
-    stall)  # wave-state PMC of the blend kernels over a short bench run (both blend backward paths)
-      for s in ${STALL_SEG:-0 1}; do
-        DGS_BLEND_SEG=$s TAG=${TAG}_seg$s PROG="bench.py --steps 6 --warmup 3 --no-cpu-baseline" PMC_TIMEOUT=150 \
-          KERNELS="blend_fwd=k_blend_fwd,blend_bwd2=k_blend_bwd2<,blend_bwd2s=k_blend_bwd2s" \
-          run 400 $O/stall_seg$s.txt bash tools/stall_pmc.sh
-        tail -30 $O/stall_seg$s.txt
-      done ;;
+    stall)  # wave-state PMC of the blend kernels over a short bench run
+      TAG=$TAG PROG="bench.py --steps 6 --warmup 3 --no-cpu-baseline" PMC_TIMEOUT=150 \
+        KERNELS="blend_fwd=k_blend_fwd,blend_bwd2=k_blend_bwd2<" \
+        run 400 $O/stall.txt bash tools/stall_pmc.sh
+      tail -30 $O/stall.txt ;;
     outlier)  # tests/diag/step_outlier.py on the composed-step case OUTLIER (default blender-cfg2)
       run 300 $O/outlier.txt python tests/diag/step_outlier.py ${OUTLIER:-blender-cfg2}
       tail -30 $O/outlier.txt ;;

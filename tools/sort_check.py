@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Renders synth-100k (800x800) forward + backward and saves image, radii and gradients to an .npz:
-python3 tools/sort_check.py OUT.npz. Run once with DGS_HIPCUB_SORT=1 and once without to check that
-the build's radix sort (radix.hip) bins exactly as hipcub::DeviceRadixSort (bitwise-equal results
-up to the order of float atomics in the blend backward, so gradients are compared to tolerance)."""
+python3 tools/sort_check.py OUT.npz. tools/blend_check.sh runs it once per library (DGS_LIB selects the
+build) and compares the two files: images and radii bitwise, gradients bitwise with DGS_DETERMINISTIC=1
+and otherwise up to the order of the float atomics in the blend backward."""
 import os
 import sys
 

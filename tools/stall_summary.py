@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel averages of the tools/stall_pmc.sh counter passes (default: the split-bf16 MLP kernels;
-KERNELS="name=substring,..." picks others, e.g. KERNELS="fwd=k_blend_fwd,bwd2=k_blend_bwd2<,bwd2s=k_blend_bwd2s")."""
+KERNELS="name=substring,..." picks others, e.g. KERNELS="fwd=k_blend_fwd,bwd2=k_blend_bwd2<")."""
 import csv
 import glob
 import os
