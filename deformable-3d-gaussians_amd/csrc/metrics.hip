@@ -1,7 +1,7 @@
 // Batched image metrics for MI355X: PSNR, SSIM and MS-SSIM of F frame pairs in one call, forward only.
 //   PSNR    utils/image_utils.py:19-21 per frame: 20 log10(1 / sqrt(mean (I-G)^2)).
-//   SSIM    utils/loss_utils.py:41-73: the quantity k_ssim_fwd (ssim.hip) sums, with its window taps
-//           and its arithmetic, without the three backward maps.
+//   SSIM    utils/loss_utils.py:41-73: the quantity k_ssim_fwd (ssim.hip) sums, with its window taps,
+//           its tile load and its per-pixel expression (ssim_tile.h), without the three backward maps.
 //   MS-SSIM pytorch_msssim.ms_ssim(data_range=1): five levels of a *valid* (unpadded) 11x11 sigma-1.5
 //           filter, avg_pool2d(2, 2, padding = side mod 2, zeros counted) between levels,
 //           prod_l relu(cs_l)^w_l * relu(ssim_4)^w_4 per channel, mean over channels.
@@ -10,8 +10,9 @@
 // pyramid (scratch), one final reduction. Tiles write partial sums; k_final adds them in a fixed order
 // in double: no atomics, results are bitwise reproducible and a frame's sums see only its own tiles.
 //
-// Tile pass = k_ssim_fwd's structure: 32x32 outputs per 256-thread workgroup from a 42x42 LDS tile,
-// separable 11-tap row pass (18 inputs in registers for 8 outputs) and column pass (14 for 4).
+// Tile pass = k_ssim_fwd's structure on ssim_tile.h's pieces: 32x32 outputs per 256-thread workgroup from
+// a 42x42 LDS tile, separable 11-tap row pass (18 inputs in registers for 8 outputs) and column pass (14
+// for 4), written out here as in k_ssim_fwd (why: ssim_tile.h).
 // The valid pass differs in the tile's origin (outputs (x, y) read inputs x..x+10, y..y+10) and in the
 // outputs that exist (w-10 by h-10). It also filters x - cx and y - cy, cx / cy = the tile's centre
 // pixel of each image: variances and the covariance do not change under a shift, and g*x^2 - mu^2 then
@@ -24,36 +25,15 @@
 #include <cmath>
 
 #include "dgs_common.h"
+#include "ssim_tile.h"
 
 namespace dgs {
-namespace ssim {
-struct Win {
-    float w[11];
-};
-Win make_window();  // ssim.hip: the loss kernels' taps
-}  // namespace ssim
-
 namespace metrics {
 
-using ssim::Win;
+using namespace ssim;  // ssim_tile.h: the tile constants, Win, load_tile, ssim_pixel, tile_sums
 
-constexpr int T = 32;         // output tile
-constexpr int R = 5;          // window radius
-constexpr int S = T + 2 * R;  // 42: input tile
-constexpr int SP = S + 1;     // padded LDS row of the input tile
-constexpr int HP = T + 1;     // padded LDS row of the row-filtered maps
-constexpr int HX = 8;         // row pass: outputs per thread
-constexpr int VY = 4;         // column pass: outputs per thread
 constexpr int LEVELS = 5;
 constexpr int MIN_SIDE = (11 - 1) * 16;  // MS-SSIM needs min(H, W) > 160
-constexpr float C1 = 0.01f * 0.01f;
-constexpr float C2 = 0.03f * 0.03f;
-
-__device__ inline float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // a product the compiler may not contract into the add or subtract that uses it
 __device__ __forceinline__ float rounded(float v) {
@@ -95,30 +75,9 @@ __global__ __launch_bounds__(256) void k_tile(int h, int w, const float *__restr
         cx = px[pc];
         cy = py[pc];
     }
-    {
-        // every load is issued before the first LDS store (ssim.hip load_tile)
-        constexpr int NIT = (S * S + 255) / 256;
-        float va[NIT], vb[NIT];
-#pragma unroll
-        for (int it = 0; it < NIT; it++) {
-            const int e = tid + 256 * it;
-            const int ly = e / S, lx = e - ly * S;
-            const int gy = oy + ly, gx = ox + lx;
-            const bool in = e < S * S && gy >= 0 && gy < h && gx >= 0 && gx < w;
-            const size_t p = in ? (size_t)gy * w + gx : 0;
-            va[it] = in ? px[p] : 0.f;
-            vb[it] = in ? py[p] : 0.f;
-        }
-#pragma unroll
-        for (int it = 0; it < NIT; it++) {
-            const int e = tid + 256 * it;
-            const int ly = e / S, lx = e - ly * S;
-            if (e < S * S) {
-                sx[0][ly][lx] = va[it] - cx;
-                sx[1][ly][lx] = vb[it] - cy;
-            }
-        }
-    }
+    const float *src[2] = {px, py};
+    const float centre[2] = {cx, cy};
+    load_tile<2, VALID>(sx, src, h, w, ox, oy, centre);
     __syncthreads();
     if (tid < S * (T / HX)) {
         const int ly = tid / (T / HX), lx0 = (tid % (T / HX)) * HX;
@@ -173,30 +132,14 @@ __global__ __launch_bounds__(256) void k_tile(int h, int w, const float *__restr
                 s0 += cs;
                 s1 += sv;
             } else {
-                // k_ssim_fwd's expression, so that this is the value fused_ssim returns
-                const float mu1 = mu[0][j], mu2 = mu[1][j];
-                const float mu1s = mu1 * mu1, mu2s = mu2 * mu2, mu12 = mu1 * mu2;
-                const float s11 = mu[2][j] - mu1s, s22 = mu[3][j] - mu2s, s12 = mu[4][j] - mu12;
-                const float n1 = 2.f * mu12 + C1, n2 = 2.f * s12 + C2;
-                const float d1 = mu1s + mu2s + C1, d2 = s11 + s22 + C2;
+                // the loss's expression, so that this is the value fused_ssim returns
                 const float d = sx[0][ly0 + j + R][lx + R] - sx[1][ly0 + j + R][lx + R];
                 s0 += d * d;
-                s1 += n1 * n2 * (1.f / (d1 * d2));
+                s1 += ssim_pixel(mu[0][j], mu[1][j], mu[2][j], mu[3][j], mu[4][j]).sv;
             }
         }
     }
-    s0 = wave_sum(s0);
-    s1 = wave_sum(s1);
-    if ((tid & 63) == 0) {
-        red[0][tid >> 6] = s0;
-        red[1][tid >> 6] = s1;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        const size_t b = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-        partial[2 * b] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-        partial[2 * b + 1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-    }
+    tile_sums(s0, s1, red, partial);
 }
 
 // avg_pool2d(kernel 2, stride 2, padding (h & 1, w & 1), count_include_pad) of both images' planes:

@@ -9,62 +9,18 @@
 // Forward: 5 maps (mu1, mu2, E[I^2], E[G^2], E[IG]) -> per pixel SSIM and the three coefficient
 // maps A, B, C of dSSIM/d(mu1, E[I^2], E[IG]) -> HBM; per-block partial sums (deterministic).
 // Backward: dSSIM_sum/dI = w*A + 2 I (w*B) + G (w*C) (window symmetric), plus the L1 sign term.
+//
+// The tile constants, the tile load, the per-pixel SSIM and the block sums are ssim_tile.h's, shared
+// with metrics.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 
 #include "dgs_common.h"
+#include "ssim_tile.h"
 
 namespace dgs {
 namespace ssim {
-
-constexpr int T = 32;            // output tile (32 x 32 pixels per 256-thread workgroup)
-constexpr int R = 5;             // window radius
-constexpr int S = T + 2 * R;     // 42: input tile with halo
-constexpr int SP = S + 1;        // padded LDS row of the input tile
-constexpr int HP = T + 1;        // padded LDS row of the row-filtered maps
-constexpr int HX = 8;            // row pass: outputs per thread (one row, 8 columns: 168 items)
-constexpr int VY = 4;            // column pass: outputs per thread (one column, 4 rows: 256 items)
-constexpr float C1 = 0.01f * 0.01f;
-constexpr float C2 = 0.03f * 0.03f;
-
-struct Win {
-    float w[11];
-};
-
-__device__ inline float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// NM maps of the halo tile (zero outside the image) from `src` planes (plane stride `plane`) into
-// LDS, 42 x 42 each. Every load of the thread is issued before the first LDS store (unrolled: a
-// rolled loop waited out one HBM round trip per 256 elements, 7 in a row)
-template <int NM>
-__device__ __forceinline__ void load_tile(float (*sm)[S][SP], const float *const src[NM], int H, int W, int x0,
-                                          int y0) {
-    constexpr int NIT = (S * S + 255) / 256;
-    float v[NIT][NM];
-#pragma unroll
-    for (int it = 0; it < NIT; it++) {
-        const int e = threadIdx.x + 256 * it;
-        const int ly = e / S, lx = e - ly * S;
-        const int gy = y0 + ly - R, gx = x0 + lx - R;
-        const bool in = e < S * S && gy >= 0 && gy < H && gx >= 0 && gx < W;
-        const size_t p = in ? (size_t)gy * W + gx : 0;
-#pragma unroll
-        for (int q = 0; q < NM; q++) v[it][q] = in ? src[q][p] : 0.f;
-    }
-#pragma unroll
-    for (int it = 0; it < NIT; it++) {
-        const int e = threadIdx.x + 256 * it;
-        const int ly = e / S, lx = e - ly * S;
-        if (e < S * S)
-#pragma unroll
-            for (int q = 0; q < NM; q++) sm[q][ly][lx] = v[it][q];
-    }
-}
 
 // forward: 5 maps (mu1, mu2, E[I^2], E[G^2], E[IG]); the products are formed on the fly from the two
 // input tiles. Row pass: each item = one tile row x 8 columns from 18 inputs held in registers;
@@ -80,7 +36,7 @@ __global__ __launch_bounds__(256) void k_ssim_fwd(int H, int W, const float *__r
     const int tid = threadIdx.x;
     const size_t plane = (size_t)H * W;
     const float *src[2] = {I + c * plane, G + c * plane};
-    load_tile<2>(sx, src, H, W, x0, y0);
+    load_tile<2>(sx, src, H, W, x0 - R, y0 - R);
     __syncthreads();
     if (tid < S * (T / HX)) {
         const int ly = tid / (T / HX), lx0 = (tid % (T / HX)) * HX;
@@ -129,36 +85,20 @@ __global__ __launch_bounds__(256) void k_ssim_fwd(int H, int W, const float *__r
         const int y = y0 + ly0 + j;
         if (x < W && y < H) {
             const float mu1 = mu[0][j], mu2 = mu[1][j];
-            const float mu1s = mu1 * mu1, mu2s = mu2 * mu2, mu12 = mu1 * mu2;
-            const float s11 = mu[2][j] - mu1s, s22 = mu[3][j] - mu2s, s12 = mu[4][j] - mu12;
-            const float n1 = 2.f * mu12 + C1, n2 = 2.f * s12 + C2;
-            const float d1 = mu1s + mu2s + C1, d2 = s11 + s22 + C2;
-            const float inv = 1.f / (d1 * d2);
-            const float sv = n1 * n2 * inv;
-            const float A = 2.f * mu2 * n2 * inv - 2.f * mu1 * sv / d1 + 2.f * mu1 * sv / d2 - mu2 * 2.f * n1 * inv;
-            const float B = -sv / d2;
-            const float Cc = 2.f * n1 * inv;
+            const Pixel t = ssim_pixel(mu1, mu2, mu[2][j], mu[3][j], mu[4][j]);
+            const float A = 2.f * mu2 * t.n2 * t.inv - 2.f * mu1 * t.sv / t.d1 + 2.f * mu1 * t.sv / t.d2 -
+                            mu2 * 2.f * t.n1 * t.inv;
+            const float B = -t.sv / t.d2;
+            const float Cc = 2.f * t.n1 * t.inv;
             const size_t p = (size_t)y * W + x;
             maps[(3 * c + 0) * plane + p] = A;
             maps[(3 * c + 1) * plane + p] = B;
             maps[(3 * c + 2) * plane + p] = Cc;
             l1 += fabsf(sx[0][ly0 + j + R][lx + R] - sx[1][ly0 + j + R][lx + R]);
-            s += sv;
+            s += t.sv;
         }
     }
-    l1 = wave_sum(l1);
-    s = wave_sum(s);
-    const int wv = tid >> 6;
-    if ((tid & 63) == 0) {
-        red[0][wv] = l1;
-        red[1][wv] = s;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        size_t b = ((size_t)c * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-        partial[2 * b] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-        partial[2 * b + 1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-    }
+    tile_sums(l1, s, red, partial);
 }
 
 // (Round 5 tried this reduction in k_ssim_fwd's last workgroup — ticket, sc1 partials — to save the
@@ -208,7 +148,7 @@ __global__ __launch_bounds__(256) void k_ssim_bwd(int H, int W, const float *__r
     const int tid = threadIdx.x;
     const size_t plane = (size_t)H * W;
     const float *src[3] = {maps + (3 * c) * plane, maps + (3 * c + 1) * plane, maps + (3 * c + 2) * plane};
-    load_tile<3>(sm, src, H, W, x0, y0);
+    load_tile<3>(sm, src, H, W, x0 - R, y0 - R);
     __syncthreads();
     if (tid < S * (T / HX)) {
         const int ly = tid / (T / HX), lx0 = (tid % (T / HX)) * HX;

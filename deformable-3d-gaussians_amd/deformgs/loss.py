@@ -60,19 +60,26 @@ def psnr(img1, img2):
 
 
 # ---- fused HIP path (libdgs_hip: dgs_l1_ssim_*) used by the training step ----
+def l1_ssim_forward(img, gt, lambda_dssim):
+    """dgs_l1_ssim_forward on contiguous fp32 device (C, H, W) images -> (out3, scratch): out3 = (loss, mean L1,
+    mean SSIM), scratch = what dgs_l1_ssim_backward reads."""
+    from . import _lib
+    lib = _lib.load()
+    _lib.require_cuda(img, gt)
+    C, H, W = img.shape[-3:]
+    scratch = torch.empty(lib.dgs_l1_ssim_scratch_floats(C, H, W), dtype=torch.float32, device=img.device)
+    out = torch.empty(3, dtype=torch.float32, device=img.device)
+    _lib.check(lib.dgs_l1_ssim_forward(C, H, W, _lib.ptr(img), _lib.ptr(gt), float(lambda_dssim), _lib.ptr(out),
+                                       _lib.ptr(scratch), _lib.stream_ptr(img.device)), "l1_ssim_forward")
+    return out, scratch
+
+
 class _FusedL1SSIM(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img, gt, lambda_dssim):
-        from . import _lib
-        lib = _lib.load()
         img = img.float().contiguous()
         gt = gt.float().contiguous()
-        _lib.require_cuda(img, gt)
-        C, H, W = img.shape[-3:]
-        scratch = torch.empty(lib.dgs_l1_ssim_scratch_floats(C, H, W), dtype=torch.float32, device=img.device)
-        out = torch.empty(3, dtype=torch.float32, device=img.device)
-        _lib.check(lib.dgs_l1_ssim_forward(C, H, W, _lib.ptr(img), _lib.ptr(gt), float(lambda_dssim), _lib.ptr(out),
-                                           _lib.ptr(scratch), _lib.stream_ptr(img.device)), "l1_ssim_forward")
+        out, scratch = l1_ssim_forward(img, gt, lambda_dssim)
         ctx.save_for_backward(img, gt, scratch)
         ctx.lam = float(lambda_dssim)
         ctx.set_materialize_grads(False)  # l1 / ssim are not differentiable: no zero-fill kernels

@@ -21,22 +21,13 @@ import os
 
 import torch
 
-from .loss import psnr
+from .loss import l1_ssim_forward, psnr
 from .png import read_png
 
 
 def fused_ssim(img, gt):
     """Mean SSIM of two (1, 3, H, W) device images from the fused L1 + SSIM forward kernel."""
-    from . import _lib
-    lib = _lib.load()
-    a, b = img[0].float().contiguous(), gt[0].float().contiguous()
-    _lib.require_cuda(a, b)
-    C, H, W = a.shape
-    scratch = torch.empty(lib.dgs_l1_ssim_scratch_floats(C, H, W), dtype=torch.float32, device=a.device)
-    out = torch.empty(3, dtype=torch.float32, device=a.device)
-    _lib.check(lib.dgs_l1_ssim_forward(C, H, W, _lib.ptr(a), _lib.ptr(b), 0.2, _lib.ptr(out), _lib.ptr(scratch),
-                                       _lib.stream_ptr(a.device)), "l1_ssim_forward")
-    return out[2]
+    return l1_ssim_forward(img[0].float().contiguous(), gt[0].float().contiguous(), 0.2)[0][2]
 
 
 def read_images(renders_dir, gt_dir, device):

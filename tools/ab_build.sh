@@ -1,7 +1,7 @@
 #!/bin/bash
-# Baseline library for A/B timing: source file $SRC (default raster) with the headers beside it, all taken
-# from git revision $REV (default HEAD), linked with the other current product objects
-# -> lib/diag/libdgs_base.so
+# Baseline library for A/B timing: the source files in $SRC (default raster; SRC="ssim metrics" for several) with
+# the headers beside them, all taken from git revision $REV (default HEAD), linked with the other current product
+# objects -> lib/diag/libdgs_base.so
 set -eu
 cd "$(dirname "$0")/.."
 SRC=${SRC:-raster}; REV=${REV:-HEAD}

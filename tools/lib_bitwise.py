@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
-"""Bitwise comparison of two builds of libdgs_hip.so on the fused MLP (a kernel restructuring that
-keeps every output tile's summation order must reproduce the previous build's bits).
+"""Bitwise comparison of two builds of libdgs_hip.so on the fused MLP or on the SSIM kernels (a kernel
+restructuring that keeps every summation order must reproduce the previous build's bits).
   python3 tools/lib_bitwise.py dump OUT.npz      (with DGS_LIB=... selecting the build)
+  python3 tools/lib_bitwise.py dump_ssim OUT.npz
   python3 tools/lib_bitwise.py cmp A.npz B.npz
-The dump runs DeformNetworkBaseline forward + backward (blender and non-blender; frame-uniform t and
+dump runs DeformNetworkBaseline forward + backward (blender and non-blender; frame-uniform t and
 per-point t; ragged N), then the same forward under torch.no_grad (the inference kernels), and stores
-the outputs and every parameter gradient."""
+the outputs and every parameter gradient. dump_ssim stores l1_ssim_loss's three outputs and dL/dimg
+(upstream gradient 1 and 3) and image_metrics' raw (F, 3 + 10 C) output, NaN slots included, on seeded
+images. cmp compares bytes, not values."""
 import os
 import sys
 
@@ -43,19 +46,51 @@ def dump(path):
     print(f"dumped {len(out)} arrays to {path}")
 
 
+def dump_ssim(path):
+    import torch
+    from deformgs.image_metrics import image_metrics
+    from deformgs.loss import l1_ssim_loss
+    dev = torch.device("cuda", 0)
+    gen = torch.Generator().manual_seed(0)
+
+    def pair(*shape):  # a target and a render close to it, as the loss and the scores see them
+        gt = torch.rand(shape, generator=gen)
+        return (gt + 0.1 * torch.randn(shape, generator=gen)).clamp(0, 1).to(dev), gt.to(dev)
+
+    out = {}
+    for shape in ((3, 800, 800), (3, 61, 83), (1, 16, 16), (3, 5, 200)):
+        img, gt = pair(*shape)
+        for up in (1.0, 3.0):
+            x = img.clone().requires_grad_(True)
+            loss, l1, s = l1_ssim_loss(x, gt)
+            (up * loss).backward()
+            key = "loss_" + "x".join(map(str, shape)) + f"_up{up:g}"
+            out[key + "/out3"] = torch.stack([loss.detach(), l1, s]).cpu().numpy()
+            out[key + "/dimg"] = x.grad.cpu().numpy()
+    # the CASES of tests/test_gpu_image_metrics.py (F, H, W; three channels), every metric; a small batch without MS-SSIM
+    for (F, H, W), names in (((3, 161, 163), ("psnr", "ssim", "ms_ssim")), ((3, 200, 176), ("psnr", "ssim", "ms_ssim")),
+                             ((1, 161, 163), ("psnr", "ssim", "ms_ssim")), ((2, 37, 45), ("psnr", "ssim"))):
+        img, gt = pair(F, 3, H, W)
+        raw = image_metrics(img, gt, names)["levels"]._base  # the (F, 3 + 10 C) tensor dgs_image_metrics wrote
+        assert raw.shape == (F, 33), raw.shape
+        out[f"metrics_{F}x3x{H}x{W}"] = raw.cpu().numpy()
+    np.savez(path, **out)
+    print(f"dumped {len(out)} arrays to {path}")
+
+
 def cmp(pa, pb):
     a, b = np.load(pa), np.load(pb)
     assert sorted(a.files) == sorted(b.files), "different keys"
     bad = [k for k in a.files if a[k].tobytes() != b[k].tobytes()]
     print(f"{len(a.files)} arrays, {len(bad)} differ bitwise")
     for k in bad[:20]:
-        d = np.abs(a[k].astype(np.float64) - b[k]).max()
+        d = np.nanmax(np.abs(a[k].astype(np.float64) - b[k]))
         print(f"  {k}: max|d| {d:.3g} (max|a| {np.abs(a[k]).max():.3g})")
     return 1 if bad else 0
 
 
 if __name__ == "__main__":
-    if sys.argv[1] == "dump":
-        dump(sys.argv[2])
+    if sys.argv[1] in ("dump", "dump_ssim"):
+        {"dump": dump, "dump_ssim": dump_ssim}[sys.argv[1]](sys.argv[2])
     else:
         sys.exit(cmp(sys.argv[2], sys.argv[3]))

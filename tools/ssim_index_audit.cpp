@@ -1,17 +1,26 @@
-// Host audit of the SSIM kernels' index arithmetic (csrc/ssim.hip; VERDICT r4 "close the r4v abort
-// from the evidence in hand"). Every thread of every workgroup of k_ssim_fwd / k_ssim_final /
-// k_ssim_bwd is replayed on the CPU with the kernels' own index expressions (copied term for term,
-// constants from ssim.hip) and every global and LDS address each thread forms is checked against the
-// extent of its buffer: the input planes (C*H*W), the scratch (3*C*H*W maps + 2*nb partials, as
-// dgs_l1_ssim_scratch_floats sizes it), the gradient, and the LDS arrays sx / sm [NM][S][SP], hq
-// [NM][S][HP], red. Usage: ssim_index_audit C H W [C H W ...]; exit 0 = every address in bounds.
-// Built and run by tests/test_ssim_index_audit.py for the shapes of tests/test_gpu_loss.py.
+// Host audit of the SSIM tile kernels' index arithmetic: the loss (csrc/ssim.hip: k_ssim_fwd / k_ssim_final /
+// k_ssim_bwd; VERDICT r4 "close the r4v abort from the evidence in hand") and the batched image metrics
+// (csrc/metrics.hip: k_tile<false>, k_tile<true>, k_pool). Every thread of every workgroup is replayed on the
+// CPU with the kernels' own index expressions and every global and LDS address each thread forms is checked
+// against the extent of its buffer. The tile constants, the tile load and the partial slot are written once,
+// in csrc/ssim_tile.h: that header is the one place audit_load_tile, audit_tile_sums and the constants below
+// must match term for term; the row and column passes (audit_row_pass / audit_col_pass) and what each kernel
+// adds around them (origin, guards, its own reads and writes, the buffer extents of
+// dgs_l1_ssim_scratch_floats and of metrics.hip's make_layout) are replayed from ssim.hip and metrics.hip.
+// Usage: ssim_index_audit <group> ...; a group is
+//   C H W            the three loss kernels on a (C, H, W) image
+//   same P H W       k_tile<false> (zero-padded pass: PSNR + SSIM) on P = F * C planes of H x W
+//   ms P H W         the MS-SSIM pyramid: k_tile<true> on each of the five levels and the four k_pool between
+// exit 0 = every address in bounds. Built and run by tests/test_ssim_index_audit.py for the shapes of
+// tests/test_gpu_loss.py and tests/test_gpu_image_metrics.py.
 #include <cstdio>
 #include <cstdlib>
 #include <cstddef>
+#include <cstring>
 
 namespace {
 constexpr int T = 32, R = 5, S = T + 2 * R, SP = S + 1, HP = T + 1, HX = 8, VY = 4;
+constexpr int LEVELS = 5;
 
 long long g_checks = 0;
 int g_fail = 0;
@@ -26,17 +35,18 @@ void chk(const char *what, long long idx, long long n, int c, int bx, int by, in
 }
 
 int div_up(int a, int b) { return (a + b - 1) / b; }
+int imin(int a, int b) { return a < b ? a : b; }
 
-// load_tile<NM>: element e of the 42x42 halo tile, global read src[q][p] only when `in`; src[q] =
-// buffer + base[q], checked against the region the map lives in (region_n)
-void audit_load_tile(int NM, const long long *base, long long region_n, int H, int W, int x0, int y0, int c, int bx,
+// load_tile<NM>: element e of the 42x42 input tile with origin (ox, oy), global read src[q][p] only when
+// `in`; src[q] = buffer + base[q], checked against the region the map lives in (region_n)
+void audit_load_tile(int NM, const long long *base, long long region_n, int H, int W, int ox, int oy, int c, int bx,
                      int by) {
     const int NIT = (S * S + 255) / 256;
     for (int tid = 0; tid < 256; tid++)
         for (int it = 0; it < NIT; it++) {
             const int e = tid + 256 * it;
             const int ly = e / S, lx = e - ly * S;
-            const int gy = y0 + ly - R, gx = x0 + lx - R;
+            const int gy = oy + ly, gx = ox + lx;
             const bool in = e < S * S && gy >= 0 && gy < H && gx >= 0 && gx < W;
             const long long p = in ? (long long)gy * W + gx : 0;
             if (in)
@@ -46,7 +56,7 @@ void audit_load_tile(int NM, const long long *base, long long region_n, int H, i
         }
 }
 
-// row pass (fwd: 2 input maps -> 5 row-filtered; bwd: 3 -> 3)
+// row pass (k_ssim_fwd, k_tile: 2 input maps -> 5 row-filtered; k_ssim_bwd: 3 -> 3)
 void audit_row_pass(int NIN, int NOUT, int c, int bx, int by) {
     for (int tid = 0; tid < 256; tid++) {
         if (!(tid < S * (T / HX))) continue;
@@ -74,7 +84,15 @@ void audit_col_pass(int NM, int c, int bx, int by) {
     }
 }
 
-int audit(int C, int H, int W) {
+// tile_sums: the wave leaders' red[.][tid >> 6] and thread 0's slot 2 * block + 1 of `partial` (partial_n floats)
+void audit_tile_sums(long long partial_n, int z, int gx, int gy, int bx, int by) {
+    for (int tid = 0; tid < 256; tid++)
+        if ((tid & 63) == 0) chk("tile_sums red", tid >> 6, 4, z, bx, by, tid);
+    const long long blk = ((long long)z * gy + by) * gx + bx;
+    chk("tile_sums partial write", 2 * blk + 1, partial_n, z, bx, by, 0);
+}
+
+int audit_loss(int C, int H, int W) {
     const long long plane = (long long)H * W;
     const int gx = div_up(W, T), gy = div_up(H, T);
     const long long nb = (long long)C * gx * gy;
@@ -87,7 +105,7 @@ int audit(int C, int H, int W) {
                 // ---- k_ssim_fwd ----
                 // src planes I + c*plane, G + c*plane: global index = c*plane + p
                 const long long fb[2] = {c * plane, c * plane};  // I + c*plane, G + c*plane
-                audit_load_tile(2, fb, img_n, H, W, x0, y0, c, bx, by);
+                audit_load_tile(2, fb, img_n, H, W, x0 - R, y0 - R, c, bx, by);
                 audit_row_pass(2, 5, c, bx, by);
                 audit_col_pass(5, c, bx, by);
                 for (int tid = 0; tid < 256; tid++) {
@@ -103,14 +121,11 @@ int audit(int C, int H, int W) {
                             chk("fwd l1 LDS read G", ((long long)1 * S + ly0 + j + R) * SP + lx + R, 2LL * S * SP, c, bx, by, tid);
                         }
                     }
-                    const int wv = tid >> 6;
-                    if ((tid & 63) == 0) chk("fwd red", wv, 4, c, bx, by, tid);
                 }
-                const long long b = ((long long)c * gy + by) * gx + bx;
-                chk("fwd partial write", 3LL * C * H * W + 2 * b + 1, scratch_n, c, bx, by, 0);
+                audit_tile_sums(2 * nb, c, gx, gy, bx, by);  // partial = scratch + 3*C*H*W, 2*nb floats
                 // ---- k_ssim_bwd ----
                 const long long bb[3] = {3LL * c * plane, (3LL * c + 1) * plane, (3LL * c + 2) * plane};  // maps
-                audit_load_tile(3, bb, 3LL * C * H * W, H, W, x0, y0, c, bx, by);
+                audit_load_tile(3, bb, 3LL * C * H * W, H, W, x0 - R, y0 - R, c, bx, by);
                 audit_row_pass(3, 3, c, bx, by);
                 audit_col_pass(3, c, bx, by);
                 for (int tid = 0; tid < 256; tid++) {
@@ -131,20 +146,108 @@ int audit(int C, int H, int W) {
     }
     return g_fail;
 }
+
+// ---- metrics.hip ----
+// k_tile<VALID> on `planes` planes of h x w; its partial sums have make_layout's extent for the pass,
+// 2 * planes * tiles(oh, ow)
+void audit_tile(bool VALID, int planes, int h, int w) {
+    const long long plane = (long long)h * w, img_n = planes * plane;
+    const int ow = VALID ? w - 2 * R : w, oh = VALID ? h - 2 * R : h;
+    const int gx = div_up(ow, T), gy = div_up(oh, T);           // the launch's grid
+    const long long partial_n = 2LL * planes * (div_up(oh, T) * div_up(ow, T));  // make_layout: 2 * planes * tiles()
+    for (int z = 0; z < planes; z++)
+        for (int by = 0; by < gy; by++)
+            for (int bx = 0; bx < gx; bx++) {
+                const int x0 = bx * T, y0 = by * T;
+                const int ox = VALID ? x0 : x0 - R, oy = VALID ? y0 : y0 - R;
+                if (VALID) {
+                    const long long pc = (long long)imin(oy + S / 2, h - 1) * w + imin(ox + S / 2, w - 1);
+                    chk("tile centre pixel", z * plane + pc, img_n, z, bx, by, -1);
+                }
+                const long long base[2] = {z * plane, z * plane};  // X + z*plane, Y + z*plane
+                audit_load_tile(2, base, img_n, h, w, ox, oy, z, bx, by);
+                audit_row_pass(2, 5, z, bx, by);
+                audit_col_pass(5, z, bx, by);
+                for (int tid = 0; tid < 256; tid++) {
+                    const int lx = tid % T, ly0 = (tid / T) * VY;
+                    const int x = x0 + lx;
+                    for (int j = 0; j < VY; j++) {
+                        const int y = y0 + ly0 + j;
+                        if (x < ow && y < oh && !VALID)
+                            for (int q = 0; q < 2; q++)
+                                chk("tile squared-error LDS read", ((long long)q * S + ly0 + j + R) * SP + lx + R, 2LL * S * SP, z, bx, by, tid);
+                    }
+                }
+                audit_tile_sums(partial_n, z, gx, gy, bx, by);
+            }
+}
+
+// k_pool: (h, w) -> (ph, pw), 64 x 4 outputs per workgroup; four source reads (when inside), one destination
+void audit_pool(int planes, int h, int w, int ph, int pw) {
+    const long long src_n = (long long)planes * h * w, dst_n = (long long)planes * ph * pw;
+    for (int z = 0; z < planes; z++)
+        for (int by = 0; by < div_up(ph, 4); by++)
+            for (int bx = 0; bx < div_up(pw, 64); bx++)
+                for (int tid = 0; tid < 256; tid++) {
+                    const int ox = bx * 64 + (tid & 63), oy = by * 4 + (tid >> 6);
+                    if (ox >= pw || oy >= ph) continue;
+                    const long long src = z * ((long long)h * w), dst = z * ((long long)ph * pw) + (long long)oy * pw + ox;
+                    const int ix = 2 * ox - (w & 1), iy = 2 * oy - (h & 1);
+                    for (int k = 0; k < 4; k++) {
+                        const int gx = ix + (k & 1), gy = iy + (k >> 1);
+                        const bool in = gx >= 0 && gx < w && gy >= 0 && gy < h;
+                        if (in) chk("pool source read", src + (long long)gy * w + gx, src_n, z, bx, by, tid);
+                    }
+                    chk("pool destination write", dst, dst_n, z, bx, by, tid);
+                }
+}
+
+int pooled(int s) { return (s + 2 * (s & 1) - 2) / 2 + 1; }  // metrics.hip
+
+void report(const char *what, long long before, int f0) {
+    std::printf("%s: %lld addresses checked, %d out of bounds\n", what, g_checks - before, g_fail - f0);
+}
 }  // namespace
 
 int main(int argc, char **argv) {
-    if (argc < 4 || (argc - 1) % 3) {
-        std::fprintf(stderr, "usage: %s C H W [C H W ...]\n", argv[0]);
-        return 2;
-    }
-    for (int a = 1; a + 2 < argc; a += 3) {
+    char what[128];
+    int a = 1;
+    while (a < argc) {
+        const bool same = !std::strcmp(argv[a], "same"), ms = !std::strcmp(argv[a], "ms");
+        if (same || ms) a++;
+        if (a + 2 >= argc) break;
         const int C = std::atoi(argv[a]), H = std::atoi(argv[a + 1]), W = std::atoi(argv[a + 2]);
-        const long long before = g_checks;
-        const int f0 = g_fail;
-        audit(C, H, W);
-        std::printf("shape (%d,%d,%d): %lld addresses checked, %d out of bounds\n", C, H, W, g_checks - before,
-                    g_fail - f0);
+        a += 3;
+        long long before = g_checks;
+        int f0 = g_fail;
+        if (same) {
+            audit_tile(false, C, H, W);
+            std::snprintf(what, sizeof what, "k_tile<false> %dx%d (%d planes)", H, W, C);
+            report(what, before, f0);
+        } else if (ms) {
+            int h = H, w = W;
+            for (int l = 0; l < LEVELS; l++) {
+                before = g_checks, f0 = g_fail;
+                audit_tile(true, C, h, w);
+                std::snprintf(what, sizeof what, "k_tile<true> level %d %dx%d (%d planes)", l, h, w, C);
+                report(what, before, f0);
+                if (l + 1 == LEVELS) break;
+                const int ph = pooled(h), pw = pooled(w);
+                before = g_checks, f0 = g_fail;
+                audit_pool(C, h, w, ph, pw);
+                std::snprintf(what, sizeof what, "k_pool %dx%d -> %dx%d (%d planes)", h, w, ph, pw, C);
+                report(what, before, f0);
+                h = ph, w = pw;
+            }
+        } else {
+            audit_loss(C, H, W);
+            std::snprintf(what, sizeof what, "shape (%d,%d,%d)", C, H, W);
+            report(what, before, f0);
+        }
+    }
+    if (a != argc || argc < 4) {
+        std::fprintf(stderr, "usage: %s <C H W | same P H W | ms P H W> ...\n", argv[0]);
+        return 2;
     }
     return g_fail ? 1 : 0;
 }
