@@ -2,13 +2,12 @@
 // down to quantised coefficients) behind two C entries, and the per-pixel rest on the device, reproducing
 // libjpeg-turbo's default decompressor (what PIL's Image.open gives) in integers, bit for bit:
 //
-// k_jpeg_idct: dequantise + the "islow" 8x8 inverse DCT (jidctint.c: CONST_BITS 13, PASS1_BITS 2). Eight
-// lanes per block, 32 blocks per 256-thread workgroup. A lane loads one row of coefficients and of the
-// quantisation table (16 bytes each: a wave reads 1 KiB of coefficients contiguously), writes the products to
-// LDS, takes a column back for pass 1, writes the workspace, takes a row back for pass 2 and stores its 8
-// output bytes as one 8-byte word into the component's block-padded sample plane. LDS rows are 9 dwords
-// apart (a block 72), so the row and the column accesses both spread over the banks. The arithmetic wraps
-// in 32 bits (unsigned adds and multiplies, an arithmetic shift of the int): on any file libjpeg decodes
+// k_jpeg_idct: dequantise + the "islow" 8x8 inverse DCT (jidctint.c: CONST_BITS 13, PASS1_BITS 2). Its FIX_*
+// constants and its layout (eight lanes per block, padded LDS rows) are jpeg_tables.h's, shared with
+// k_jpeg_transform of jpeg_encode.hip. A lane loads one row of coefficients and of the quantisation table (16
+// bytes each: a wave reads 1 KiB of coefficients contiguously), writes the products to LDS, takes a column back
+// for pass 1, writes the workspace, takes a row back for pass 2 and stores its 8 output bytes as one 8-byte
+// word into the component's block-padded sample plane. The arithmetic wraps in 32 bits (unsigned adds and multiplies, an arithmetic shift of the int): on any file libjpeg decodes
 // without overflow this is its result, and on hostile coefficients it is defined and equals
 // deformgs/jpeg.py. The zero-AC shortcuts of jidctint.c give the numbers of the full path: no branch.
 // Output: clamp(s + 128, 0, 255) with s the descaled value as a signed 10-bit number, the effect of
@@ -35,33 +34,34 @@ static_assert(offsetof(dgs_jpeg_info, qt) == offsetof(dgs_jpeg::Info, qt), "dgs_
 
 namespace dgs {
 
-constexpr int JPEG_WG_BLOCKS = 32;   // 8x8 blocks per 256-thread workgroup
-constexpr int JPEG_LDS_ROW = 9;      // dwords between the rows of a block in LDS
-constexpr int JPEG_LDS_BLOCK = 72;
+using dgs_jpeg::LDS_ROW;
+using dgs_jpeg::WG_BLOCKS;
+constexpr int LDS_BLOCK = 8 * LDS_ROW;  // dwords between two blocks in LDS
 
 // One 8-point pass of jpeg_idct_islow; the sums wrap in 32 bits, the descale is an arithmetic shift.
 template <int SHIFT>
 __device__ inline void idct8(const int (&in)[8], int (&out)[8]) {
+    using namespace dgs_jpeg;  // FIX_*
     typedef uint32_t u;
     const u x0 = (u)in[0], x1 = (u)in[1], x2 = (u)in[2], x3 = (u)in[3], x4 = (u)in[4], x5 = (u)in[5], x6 = (u)in[6],
             x7 = (u)in[7];
-    u z1 = (x2 + x6) * 4433u;                    // FIX_0_541196100
-    const u e2 = z1 - x6 * 15137u;               // FIX_1_847759065
-    const u e3 = z1 + x2 * 6270u;                // FIX_0_765366865
+    u z1 = (x2 + x6) * (u)FIX_0_541196100;
+    const u e2 = z1 - x6 * (u)FIX_1_847759065;
+    const u e3 = z1 + x2 * (u)FIX_0_765366865;
     const u e0 = (x0 + x4) << 13, e1 = (x0 - x4) << 13;
     const u t10 = e0 + e3, t13 = e0 - e3, t11 = e1 + e2, t12 = e1 - e2;
     u t0 = x7, t1 = x5, t2 = x3, t3 = x1;
     z1 = t0 + t3;
     u z2 = t1 + t2, z3 = t0 + t2, z4 = t1 + t3;
-    const u z5 = (z3 + z4) * 9633u;              // FIX_1_175875602
-    t0 *= 2446u;                                 // FIX_0_298631336
-    t1 *= 16819u;                                // FIX_2_053119869
-    t2 *= 25172u;                                // FIX_3_072711026
-    t3 *= 12299u;                                // FIX_1_501321110
-    z1 = 0u - z1 * 7373u;                        // FIX_0_899976223
-    z2 = 0u - z2 * 20995u;                       // FIX_2_562915447
-    z3 = z5 - z3 * 16069u;                       // FIX_1_961570560
-    z4 = z5 - z4 * 3196u;                        // FIX_0_390180644
+    const u z5 = (z3 + z4) * (u)FIX_1_175875602;
+    t0 *= (u)FIX_0_298631336;
+    t1 *= (u)FIX_2_053119869;
+    t2 *= (u)FIX_3_072711026;
+    t3 *= (u)FIX_1_501321110;
+    z1 = 0u - z1 * (u)FIX_0_899976223;
+    z2 = 0u - z2 * (u)FIX_2_562915447;
+    z3 = z5 - z3 * (u)FIX_1_961570560;
+    z4 = z5 - z4 * (u)FIX_0_390180644;
     t0 += z1 + z3;
     t1 += z2 + z4;
     t2 += z2 + z3;
@@ -82,9 +82,9 @@ __device__ inline void idct8(const int (&in)[8], int (&out)[8]) {
 __global__ __launch_bounds__(256) void k_jpeg_idct(long long total_blocks, int per_image, int nbY, int nbC, int bwY,
                                                    int bwC, const int16_t *__restrict__ coef,
                                                    const uint16_t *__restrict__ qt, uint8_t *__restrict__ planes) {
-    __shared__ int lds[JPEG_WG_BLOCKS * JPEG_LDS_BLOCK];
+    __shared__ int lds[WG_BLOCKS * LDS_BLOCK];
     const int lb = threadIdx.x >> 3, l = threadIdx.x & 7;
-    long long g = (long long)blockIdx.x * JPEG_WG_BLOCKS + lb;
+    long long g = (long long)blockIdx.x * WG_BLOCKS + lb;
     const bool live = g < total_blocks;
     if (!live) g = total_blocks - 1;  // clamped: the loads stay inside the buffers, nothing is stored
     const long long img = g / per_image;
@@ -96,23 +96,23 @@ __global__ __launch_bounds__(256) void k_jpeg_idct(long long total_blocks, int p
     const int4 cv = *reinterpret_cast<const int4 *>(coef + g * 64 + l * 8);
     const int4 qv = *reinterpret_cast<const int4 *>(qt + (img * 3 + c) * 64 + l * 8);
     const int cw[4] = {cv.x, cv.y, cv.z, cv.w}, qw[4] = {qv.x, qv.y, qv.z, qv.w};
-    int *blk = lds + lb * JPEG_LDS_BLOCK;
+    int *blk = lds + lb * LDS_BLOCK;
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-        blk[l * JPEG_LDS_ROW + 2 * j] = (int)((uint32_t)(int)(int16_t)(cw[j] & 0xffff) * ((uint32_t)qw[j] & 0xffffu));
-        blk[l * JPEG_LDS_ROW + 2 * j + 1] = (int)((uint32_t)(cw[j] >> 16) * ((uint32_t)qw[j] >> 16));
+        blk[l * LDS_ROW + 2 * j] = (int)((uint32_t)(int)(int16_t)(cw[j] & 0xffff) * ((uint32_t)qw[j] & 0xffffu));
+        blk[l * LDS_ROW + 2 * j + 1] = (int)((uint32_t)(cw[j] >> 16) * ((uint32_t)qw[j] >> 16));
     }
     __syncthreads();
     int x[8], o[8];
 #pragma unroll
-    for (int k = 0; k < 8; k++) x[k] = blk[k * JPEG_LDS_ROW + l];  // column l
+    for (int k = 0; k < 8; k++) x[k] = blk[k * LDS_ROW + l];  // column l
     idct8<13 - 2>(x, o);
     __syncthreads();
 #pragma unroll
-    for (int k = 0; k < 8; k++) blk[k * JPEG_LDS_ROW + l] = o[k];
+    for (int k = 0; k < 8; k++) blk[k * LDS_ROW + l] = o[k];
     __syncthreads();
 #pragma unroll
-    for (int j = 0; j < 8; j++) x[j] = blk[l * JPEG_LDS_ROW + j];  // row l
+    for (int j = 0; j < 8; j++) x[j] = blk[l * LDS_ROW + j];  // row l
     idct8<13 + 2 + 3>(x, o);
     uint32_t w[2] = {0u, 0u};
 #pragma unroll
@@ -200,12 +200,12 @@ extern "C" int dgs_ingest_jpeg(int B, int W, int H, int hs, int vs, const int16_
     const int bwY = mw * hs, bhY = mh * vs, bwC = mw, bhC = mh;
     const long long nbY = (long long)bwY * bhY, nbC = (long long)bwC * bhC, per_image = nbY + 2 * nbC;
     const long long total_blocks = per_image * B, total_px = (long long)B * W * H;
-    if (per_image > 2147483647LL || total_blocks > 2147483647LL * dgs::JPEG_WG_BLOCKS || total_px > 2147483647LL * 256) {
+    if (per_image > 2147483647LL || total_blocks > 2147483647LL * dgs::WG_BLOCKS || total_px > 2147483647LL * 256) {
         dgs::set_error("dgs_ingest_jpeg: batch too large for one launch");
         return DGS_ERR_UNSUPPORTED;
     }
     hipStream_t stream = (hipStream_t)stream_;
-    hipLaunchKernelGGL(dgs::k_jpeg_idct, dim3((unsigned)((total_blocks + dgs::JPEG_WG_BLOCKS - 1) / dgs::JPEG_WG_BLOCKS)),
+    hipLaunchKernelGGL(dgs::k_jpeg_idct, dim3((unsigned)((total_blocks + dgs::WG_BLOCKS - 1) / dgs::WG_BLOCKS)),
                        dim3(256), 0, stream, total_blocks, (int)per_image, (int)nbY, (int)nbC, bwY, bwC, coef, qtables,
                        scratch);
     DGS_LAUNCH_CHECK("k_jpeg_idct", false, stream);

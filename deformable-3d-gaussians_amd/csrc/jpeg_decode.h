@@ -1,6 +1,7 @@
 // Host JPEG front end: marker parsing and Huffman decoding of baseline / extended sequential JPEG files
 // down to quantised coefficients (deformgs/jpeg.py is the same thing in Python). Everything per pixel is
-// the device's work (jpeg.hip). Plain C++17, header-only, no HIP includes, no globals: thread-safe.
+// the device's work (jpeg.hip). Plain C++17, header-only, no HIP includes, no globals: thread-safe. The zigzag
+// order is jpeg_tables.h's.
 //
 // This parser reads user files: every byte is fetched through a bounds check (Reader::byte / Bits::fill),
 // every table index comes from a masked or range-checked value, and every failure is a message, never a
@@ -18,6 +19,8 @@
 #include <cstring>
 #include <string>
 
+#include "jpeg_tables.h"  // ZIGZAG
+
 namespace dgs_jpeg {
 
 // include/dgs.h dgs_jpeg_info, field for field
@@ -30,10 +33,6 @@ struct Info {
 };
 
 constexpr int MAX_DIM = 65535;
-
-static const uint8_t ZIGZAG[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                   41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                   30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
 struct Huffman {
     bool defined = false;

@@ -4,7 +4,7 @@
 // libjpeg-turbo's default compressor in integers (tests/jpeg_encode_ref.py is the numpy restatement). Four launches on
 // one stream, no host wait, no floating point, no atomics to global memory: the bytes are bitwise reproducible.
 //
-//   k_jpeg_transform  eight lanes per 8x8 block, 32 blocks per workgroup. Lane r converts row r of the block to its
+//   k_jpeg_transform  eight lanes per 8x8 block (jpeg_tables.h: k_jpeg_idct's layout). Lane r converts row r to its
 //                     component (jccolor.c in 16-bit fixed point; chroma of a subsampled frame is the h2v1 / h2v2 box
 //                     of jcsample.c with the 0,1 / 1,2 alternating bias, pixel coordinates clamped to the image, rows
 //                     past the component's height taking its last row), level-shifts and runs the row pass of
@@ -14,21 +14,26 @@
 //                     computed from the block whose DC it repeats, and its AC zeroed.
 //   k_jpeg_entropy    one workgroup per restart segment = MCU row, one thread per block, JE_NT blocks at a time:
 //                     the blocks' coefficients are staged in LDS in zigzag order, each thread counts its block's
-//                     bits, a prefix scan gives the bit offsets, the bits are ORed into an LDS image (most
-//                     significant bit first), and the whole bytes of the image are counted for 0xFF, scanned and,
+//                     bits, a prefix scan gives the bit offsets, the bits are ORed into an LDS image (codec_bits.h's
+//                     scan and bit writer, most significant bit first), and the whole bytes of the image are counted for 0xFF, scanned and,
 //                     in the second launch, scattered with their stuffed 0x00. The bits of a byte that is not yet
 //                     whole carry into the next round; the last byte is padded with ones. First launch (WRITE =
 //                     false): the segment's stuffed byte count. Second launch: the bytes, at their final place.
 //   k_jpeg_scan       exclusive prefix sum of the segments' byte counts (+ 2 for the RSTm after all but a frame's
-//                     last), the frames' offsets and true lengths, and the flag of a frame that does not fit.
+//                     last; codec_bits.h segment_offsets), the frames' offsets and true lengths, and the flag of a frame that does not fit.
 // Running the entropy coder twice costs its time again but needs no slot per segment sized for the worst case (208
 // bytes a block before stuffing: 10 bytes a pixel at 4:4:4), which is what the capacity argument is there to avoid.
+#include "codec_bits.h"
 #include "dgs_common.h"
+#include "jpeg_tables.h"
 
 namespace dgs {
 namespace {
 
-constexpr int JE_NT = 128;                       // threads = blocks per round of k_jpeg_entropy
+using dgs_jpeg::LDS_ROW;
+using dgs_jpeg::WG_BLOCKS;
+
+constexpr int JE_NT = 128;                      // threads = blocks per round of k_jpeg_entropy
 constexpr int JE_CSTRIDE = 66;                   // int16 per staged block: 33 words, odd, so lanes hit distinct banks
 constexpr int JE_BLOCK_BITS = 20 + 63 * 26;      // DC: 9 + 11 bits; AC: 16 + 10 bits each
 constexpr int JE_IMG_WORDS = (JE_NT * JE_BLOCK_BITS + 7 + 31) / 32 + 1;
@@ -62,9 +67,7 @@ __constant__ uint8_t HUFF_AC_CHROMA[162] = {
     0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda,
     0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa};
 
-__constant__ uint8_t JE_ZIGZAG[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                      41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                      30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+__constant__ uint8_t JE_ZIGZAG[64] = {DGS_JPEG_ZIGZAG_ORDER};
 
 struct QTables {
     uint16_t q[2][64];
@@ -95,6 +98,7 @@ __device__ inline int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; 
 // jfdctint.c, one 8-point pass. FIRST: the row pass (results scaled up by 4); else the column pass.
 template <bool FIRST>
 __device__ inline void fdct8(int *d) {
+    using namespace dgs_jpeg;  // FIX_*
     constexpr int SH = FIRST ? 13 - 2 : 13 + 2;
     const int t0 = d[0] + d[7], t7 = d[0] - d[7], t1 = d[1] + d[6], t6 = d[1] - d[6];
     const int t2 = d[2] + d[5], t5 = d[2] - d[5], t3 = d[3] + d[4], t4 = d[3] - d[4];
@@ -106,17 +110,17 @@ __device__ inline void fdct8(int *d) {
         d[0] = descale(t10 + t11, 2);
         d[4] = descale(t10 - t11, 2);
     }
-    int z1 = (t12 + t13) * 4433;
-    d[2] = descale(z1 + t13 * 6270, SH);
-    d[6] = descale(z1 - t12 * 15137, SH);
+    int z1 = (t12 + t13) * FIX_0_541196100;
+    d[2] = descale(z1 + t13 * FIX_0_765366865, SH);
+    d[6] = descale(z1 - t12 * FIX_1_847759065, SH);
     z1 = t4 + t7;
     int z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7;
-    const int z5 = (z3 + z4) * 9633;
-    const int a4 = t4 * 2446, a5 = t5 * 16819, a6 = t6 * 25172, a7 = t7 * 12299;
-    z1 *= -7373;
-    z2 *= -20995;
-    z3 = z3 * -16069 + z5;
-    z4 = z4 * -3196 + z5;
+    const int z5 = (z3 + z4) * FIX_1_175875602;
+    const int a4 = t4 * FIX_0_298631336, a5 = t5 * FIX_2_053119869, a6 = t6 * FIX_3_072711026, a7 = t7 * FIX_1_501321110;
+    z1 *= -FIX_0_899976223;
+    z2 *= -FIX_2_562915447;
+    z3 = z3 * -FIX_1_961570560 + z5;
+    z4 = z4 * -FIX_0_390180644 + z5;
     d[7] = descale(a4 + z1 + z3, SH);
     d[5] = descale(a5 + z2 + z4, SH);
     d[3] = descale(a6 + z2 + z3, SH);
@@ -124,11 +128,11 @@ __device__ inline void fdct8(int *d) {
 }
 
 __global__ __launch_bounds__(256) void k_jpeg_transform(Geo g, QTables qt, const uint8_t *in, int16_t *coef) {
-    __shared__ int ws[32][8][9];
-    __shared__ __attribute__((aligned(16))) int16_t qs[32][64];
+    __shared__ int ws[WG_BLOCKS][8][LDS_ROW];
+    __shared__ __attribute__((aligned(16))) int16_t qs[WG_BLOCKS][64];
     const int t = threadIdx.x, slot = t >> 3, r = t & 7;
     const long long n_blocks = (long long)g.F * g.total;
-    long long id = (long long)blockIdx.x * 32 + slot;
+    long long id = (long long)blockIdx.x * WG_BLOCKS + slot;
     const bool live = id < n_blocks;
     if (!live) id = n_blocks - 1;
     const int f = (int)(id / g.total);
@@ -203,27 +207,7 @@ __global__ __launch_bounds__(256) void k_jpeg_transform(Geo g, QTables qt, const
 
 // ---- entropy ----
 
-// ORs bits into the zeroed image, most significant bit first. A thread's bits are contiguous: only its first and
-// last word are shared with a neighbour, the LDS atomics cover those.
-struct BitWriter {
-    unsigned *img;
-    unsigned long long acc;
-    int nacc;
-    unsigned w;
-    __device__ BitWriter(unsigned *o, unsigned pos) : img(o), acc(0), nacc((int)(pos & 31)), w(pos >> 5) {}
-    __device__ void put(unsigned v, int n) {  // n <= 26, v < 2^n
-        acc = (acc << n) | v;
-        nacc += n;
-        if (nacc >= 32) {
-            nacc -= 32;
-            atomicOr(&img[w++], (unsigned)(acc >> nacc));
-            acc &= (1ull << nacc) - 1;
-        }
-    }
-    __device__ void flush() {
-        if (nacc > 0 && acc) atomicOr(&img[w], (unsigned)(acc << (32 - nacc)));
-    }
-};
+using BitWriter = codec::BitWriter<true>;  // put: <= 16 + 10 = 26 bits
 
 __device__ inline int bit_length(int a) { return 32 - __clz(a); }  // a >= 0; 0 -> 0
 
@@ -252,20 +236,6 @@ __device__ inline void code_block(const int16_t *zz, int pred, const unsigned *d
         run = 0;
     }
     if (run) put(ac[0] & 0xFFFFu, (int)(ac[0] >> 16));
-}
-
-// inclusive prefix sum over the JE_NT threads; sc has JE_NT entries
-__device__ inline unsigned block_scan(unsigned v, unsigned *sc, int t) {
-    __syncthreads();  // sc free again
-    sc[t] = v;
-    __syncthreads();
-    for (int d = 1; d < JE_NT; d <<= 1) {
-        const unsigned x = sc[t], y = t >= d ? sc[t - d] : 0u;
-        __syncthreads();
-        sc[t] = x + y;
-        __syncthreads();
-    }
-    return sc[t];
 }
 
 __device__ inline unsigned img_byte(const unsigned *img, unsigned i) { return (img[i >> 2] >> (24 - 8 * (i & 3))) & 255u; }
@@ -339,7 +309,7 @@ __global__ __launch_bounds__(JE_NT) void k_jpeg_entropy(Geo g, const int16_t *co
         const int pred = prev >= 0 ? (int)fc[(size_t)prev * 64] : 0;
         unsigned bits = 0;
         if (t < nb) code_block(zz + t * JE_CSTRIDE, pred, dc, ac, [&](unsigned, int n) { bits += (unsigned)n; });
-        const unsigned incl = block_scan(bits, sc, t);
+        const unsigned incl = codec::block_scan<JE_NT>(bits, sc, t);
         unsigned total = carry_bits + sc[JE_NT - 1];
         if (t == 0 && carry_bits) atomicOr(&img[0], carry_val << (32 - carry_bits));
         if (t < nb) {
@@ -361,7 +331,7 @@ __global__ __launch_bounds__(JE_NT) void k_jpeg_entropy(Geo g, const int16_t *co
         const unsigned lo = min(nbytes, (unsigned)t * per), hi = min(nbytes, lo + per);
         unsigned ff = 0;
         for (unsigned i = lo; i < hi; ++i) ff += img_byte(img, i) == 255u;
-        const unsigned ff_incl = block_scan(ff, sc, t);
+        const unsigned ff_incl = codec::block_scan<JE_NT>(ff, sc, t);
         if (WRITE) {
             uint8_t *o = out + dst + written + lo + (ff_incl - ff);
             for (unsigned i = lo; i < hi; ++i) {
@@ -393,24 +363,9 @@ __global__ __launch_bounds__(1024) void k_jpeg_scan(long long G, int mh, int F, 
                                                     int64_t *out_offsets, int64_t *out_lengths, int *flags) {
     __shared__ unsigned long long part[1024];
     const int t = threadIdx.x;
-    const long long per = (G + 1023) / 1024;
-    const long long i0 = min(G, t * per), i1 = min(G, i0 + per);
-    unsigned long long s = 0;
-    for (long long i = i0; i < i1; ++i) s += seg_bytes[i] + ((i % mh) != mh - 1 ? 2u : 0u);
-    part[t] = s;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const unsigned long long x = part[t], y = t >= d ? part[t - d] : 0;
-        __syncthreads();
-        part[t] = x + y;
-        __syncthreads();
-    }
-    unsigned long long run = part[t] - s;
-    for (long long i = i0; i < i1; ++i) {
-        seg_off[i] = run;
-        run += seg_bytes[i] + ((i % mh) != mh - 1 ? 2u : 0u);
-    }
-    if (t == 1023) seg_off[G] = part[1023];
+    const unsigned long long total = codec::segment_offsets(
+        G, [&](long long i) { return seg_bytes[i] + ((i % mh) != mh - 1 ? 2u : 0u); }, seg_off, part);
+    if (t == 1023) seg_off[G] = total;
     __syncthreads();  // one workgroup: its global writes are visible to it behind the barrier
     for (int f = t; f < F; f += 1024) {
         const unsigned long long a = seg_off[(long long)f * mh], b = seg_off[(long long)(f + 1) * mh];
@@ -471,7 +426,8 @@ extern "C" int dgs_jpeg_encode(int F, int H, int W, int hs, int vs, const uint8_
     }
     const long long G = (long long)F * g.mh;
     const long long n_blocks = (long long)F * g.total;
-    if (G > dgs::JE_MAX_SEGMENTS || (n_blocks + 31) / 32 > 0x7fffffffll) {
+    const long long n_wg = (n_blocks + dgs_jpeg::WG_BLOCKS - 1) / dgs_jpeg::WG_BLOCKS;
+    if (G > dgs::JE_MAX_SEGMENTS || n_wg > 0x7fffffffll) {
         dgs::set_error("dgs_jpeg_encode: batch too large for one launch (encode it in chunks)");
         return DGS_ERR_UNSUPPORTED;
     }
@@ -480,7 +436,7 @@ extern "C" int dgs_jpeg_encode(int F, int H, int W, int hs, int vs, const uint8_
     unsigned *seg_bytes = (unsigned *)(scratch + dgs::align16((size_t)n_blocks * 64 * sizeof(int16_t)));
     unsigned long long *seg_off = (unsigned long long *)((uint8_t *)seg_bytes + dgs::align16((size_t)G * sizeof(unsigned)));
     const unsigned long long cap = out_capacity;
-    hipLaunchKernelGGL(dgs::k_jpeg_transform, dim3((unsigned)((n_blocks + 31) / 32)), dim3(256), 0, stream, g, qt, in, coef);
+    hipLaunchKernelGGL(dgs::k_jpeg_transform, dim3((unsigned)n_wg), dim3(256), 0, stream, g, qt, in, coef);
     DGS_LAUNCH_CHECK("k_jpeg_transform", false, stream);
     hipLaunchKernelGGL(dgs::k_jpeg_entropy<false>, dim3((unsigned)G), dim3(dgs::JE_NT), 0, stream, g, (const int16_t *)coef,
                        seg_bytes, (const unsigned long long *)seg_off, out, cap);

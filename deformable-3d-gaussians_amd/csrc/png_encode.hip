@@ -17,7 +17,7 @@
 //                  image (<= n + 5 bytes, or it is stored) take 66 KiB of LDS, so two workgroups share a CU's
 //                  160 KiB; the constant part of a block header (~170 bytes: code lengths at 4 bits each under a
 //                  fixed, complete code-length code) stays near 0.5 % of a segment. 16 KiB would double that.
-//   k_png_scan     exclusive prefix sum of the segments' byte counts (one workgroup).
+//   k_png_scan     exclusive prefix sum of the segments' byte counts (codec_bits.h segment_offsets).
 //   k_png_pack     gathers the segments behind the zlib header 78 01, combines the Adler partials per frame
 //                  (adler32_combine's rule) and writes each frame's offset and length.
 //
@@ -27,10 +27,16 @@
 // inflate rejects an incomplete literal/length code as well as an over-subscribed one. The shortest unit left is
 // always that of a longest code, so the fill always ends exactly. The distance code is the single code 0 with one
 // bit, the one incomplete code inflate accepts, present whether or not the segment has a match.
+//
+// The block scan, the segment-offset sum and the bit writer (here least significant bit first) are codec_bits.h's,
+// shared with jpeg_encode.hip.
+#include "codec_bits.h"
 #include "dgs_common.h"
 
 namespace dgs {
 namespace {
+
+using codec::put_at;
 
 constexpr int PNG_SEG = 32768;                 // bytes of filtered stream per deflate segment
 constexpr int PNG_NT = 512;                    // threads of k_png_deflate
@@ -172,34 +178,6 @@ __device__ inline void walk(const uint8_t *buf, int n, int t, int prev_start, in
     }
 }
 
-// ORs the low nbits (<= 32) of v into the zeroed bit image at bit pos
-__device__ inline void put_at(unsigned *outw, unsigned pos, unsigned v, int nbits) {
-    const unsigned long long x = (unsigned long long)v << (pos & 31);
-    (void)nbits;
-    if ((unsigned)x) atomicOr(&outw[pos >> 5], (unsigned)x);
-    if ((unsigned)(x >> 32)) atomicOr(&outw[(pos >> 5) + 1], (unsigned)(x >> 32));
-}
-
-struct BitWriter {
-    unsigned *outw;
-    unsigned long long acc;
-    int nacc;
-    unsigned w;
-    __device__ BitWriter(unsigned *o, unsigned pos) : outw(o), acc(0), nacc((int)(pos & 31)), w(pos >> 5) {}
-    __device__ void put(unsigned v, int n) {  // n <= 21
-        acc |= (unsigned long long)v << nacc;
-        nacc += n;
-        if (nacc >= 32) {
-            atomicOr(&outw[w++], (unsigned)acc);
-            acc >>= 32;
-            nacc -= 32;
-        }
-    }
-    __device__ void flush() {
-        if (nacc > 0 && (unsigned)acc) atomicOr(&outw[w], (unsigned)acc);
-    }
-};
-
 __device__ inline unsigned long long block_sum(unsigned long long v, unsigned long long *red, int t) {
     for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
     __syncthreads();  // red free again
@@ -334,7 +312,9 @@ __global__ __launch_bounds__(PNG_NT) void k_png_deflate(int nseg, long long fbyt
     sa[t] = ls;
     sb[t] = fs;
     __syncthreads();
-    for (int d = 1; d < PNG_NT; d <<= 1) {  // running maximum of sa, running minimum of sb from the right
+    // running maximum of sa, running minimum of sb from the right: two arrays and two directions under one pair of
+    // barriers per step, which is why this is not codec::block_scan (codec_bits.h)
+    for (int d = 1; d < PNG_NT; d <<= 1) {
         const int x = sa[t], y = t >= d ? sa[t - d] : -1;
         const int u = sb[t], w = t + d < PNG_NT ? sb[t + d] : n;
         __syncthreads();
@@ -366,16 +346,8 @@ __global__ __launch_bounds__(PNG_NT) void k_png_deflate(int nseg, long long fbyt
              len_symbol(len, sym, eb, ev);
              bits += (code[sym] >> 16) + (unsigned)eb + 1u;
          });
-    sa[t] = (int)bits;
-    __syncthreads();
-    for (int d = 1; d < PNG_NT; d <<= 1) {
-        const int x = sa[t], y = t >= d ? sa[t - d] : 0;
-        __syncthreads();
-        sa[t] = x + y;
-        __syncthreads();
-    }
+    const unsigned my_bit = (unsigned)codec::block_scan<PNG_NT>((int)bits, sa, t) - bits;
     const unsigned tokbits = (unsigned)sa[PNG_NT - 1];
-    const unsigned my_bit = (unsigned)sa[t] - bits;
     const unsigned hdr_bits = 74u + 4u * (unsigned)(hlit + 1);
     const unsigned eob_len = code[PNG_EOB] >> 16;
     const unsigned end_bits = hdr_bits + tokbits + eob_len;
@@ -397,7 +369,7 @@ __global__ __launch_bounds__(PNG_NT) void k_png_deflate(int nseg, long long fbyt
             const unsigned l = t < hlit ? code[t] >> 16 : 1u;
             put_at(outw, 74u + 4u * (unsigned)t, __brev(l) >> 28, 4);
         }
-        BitWriter bw(outw, hdr_bits + my_bit);
+        codec::BitWriter<false> bw(outw, hdr_bits + my_bit);  // put: <= 15 + 5 + 1 = 21 bits
         walk(buf, n, t, prev_start, next_start, [&](int v) { bw.put(code[v] & 0xFFFFu, (int)(code[v] >> 16)); },
              [&](int len) {
                  int sym, eb, ev;
@@ -431,24 +403,7 @@ __global__ __launch_bounds__(PNG_NT) void k_png_deflate(int nseg, long long fbyt
 
 __global__ __launch_bounds__(1024) void k_png_scan(long long G, const uint4 *meta, unsigned long long *seg_off) {
     __shared__ unsigned long long part[1024];
-    const int t = threadIdx.x;
-    const long long per = (G + 1023) / 1024;
-    const long long i0 = min(G, t * per), i1 = min(G, i0 + per);
-    unsigned long long s = 0;
-    for (long long i = i0; i < i1; ++i) s += meta[i].x;
-    part[t] = s;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const unsigned long long x = part[t], y = t >= d ? part[t - d] : 0;
-        __syncthreads();
-        part[t] = x + y;
-        __syncthreads();
-    }
-    unsigned long long run = part[t] - s;
-    for (long long i = i0; i < i1; ++i) {
-        seg_off[i] = run;
-        run += meta[i].x;
-    }
+    codec::segment_offsets(G, [&](long long i) { return meta[i].x; }, seg_off, part);
 }
 
 __global__ __launch_bounds__(256) void k_png_pack(int nseg, const uint8_t *slots, const uint4 *meta,

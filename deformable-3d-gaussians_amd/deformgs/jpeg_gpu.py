@@ -13,7 +13,7 @@ import struct
 import numpy as np
 import torch
 
-from . import _lib
+from . import _encode, _lib
 from .jpeg import ZIGZAG
 
 SAMPLING = {"4:4:4": (1, 1), "4:2:2": (2, 1), "4:2:0": (2, 2)}
@@ -76,12 +76,7 @@ def jfif_header(width, height, hs, vs, qt):
 
 
 def _check(frames, subsampling):
-    if not isinstance(frames, torch.Tensor):
-        raise ValueError(f"encode_frames takes a device uint8 tensor, got {type(frames).__name__}")
-    if not frames.is_cuda:
-        raise ValueError("encode_frames takes a device (HIP) tensor; got a CPU tensor")
-    if frames.dtype != torch.uint8:
-        raise ValueError(f"encode_frames takes uint8 frames, got {frames.dtype}")
+    _encode.check_frames(frames)
     if frames.ndim == 3:
         raise ValueError(f"encode_frames takes (F, H, W, 3) RGB frames; grey (F, H, W) frames {tuple(frames.shape)} are "
                          "not written as JPEG (grayscale JPEG is unsupported, as in deformgs.jpeg)")
@@ -134,24 +129,17 @@ def encode_frames(frames, quality=90, subsampling="4:2:0", capacity=None):
     lengths, then the packed compressed bytes; no raw frame. Where the frames did not all fit the capacity (noise at
     a high quality), the call is repeated once with the exact total it has just read."""
     out, offsets, lengths, _ = encode_streams(frames, quality, subsampling, capacity)
-    where = torch.stack([offsets, lengths]).cpu().tolist()
-    total = where[0][-1] + where[1][-1]
+    spans, total = _encode.fetch_spans(offsets, lengths)
     if total > (out.numel() if capacity is None else capacity):
         out, offsets, lengths, _ = encode_streams(frames, quality, subsampling, total)
-        where = torch.stack([offsets, lengths]).cpu().tolist()
-        assert where[0][-1] + where[1][-1] == total
-    packed = out[:total].cpu().numpy().tobytes()
+        spans, again = _encode.fetch_spans(offsets, lengths)
+        assert again == total
+    packed = _encode.fetch_bytes(out, total)
     F, H, W = frames.shape[:3]
     head = jfif_header(W, H, *SAMPLING[subsampling], quant_tables(quality))
-    return [b"".join((head, packed[o:o + n], b"\xff\xd9")) for o, n in zip(*where)]
+    return [b"".join((head, packed[o:o + n], b"\xff\xd9")) for o, n in spans]
 
 
 def write_frames(paths, frames, quality=90, subsampling="4:2:0"):
     """Writes frame i to paths[i]."""
-    paths = list(paths)
-    _check(frames, subsampling)
-    if len(paths) != frames.shape[0]:
-        raise ValueError(f"write_frames: {len(paths)} paths for {frames.shape[0]} frames")
-    for path, data in zip(paths, encode_frames(frames, quality, subsampling)):
-        with open(path, "wb") as f:
-            f.write(data)
+    _encode.write_files(paths, encode_frames(frames, quality, subsampling))

@@ -9,18 +9,12 @@ import zlib
 
 import torch
 
-from . import _lib
+from . import _encode, _lib
 from .png import _SIG, _chunk
 
 
 def _check(frames):
-    if not isinstance(frames, torch.Tensor):
-        raise ValueError(f"encode_frames takes a device uint8 tensor, got {type(frames).__name__}")
-    if not frames.is_cuda:
-        raise ValueError("encode_frames takes a device (HIP) tensor; got a CPU tensor (deformgs.png.encode_png "
-                         "is the host writer)")
-    if frames.dtype != torch.uint8:
-        raise ValueError(f"encode_frames takes uint8 frames, got {frames.dtype}")
+    _encode.check_frames(frames, " (deformgs.png.encode_png is the host writer)")
     if not (frames.ndim == 3 or (frames.ndim == 4 and frames.shape[3] == 3)) or min(frames.shape) < 1:
         raise ValueError(f"encode_frames takes (F, H, W, 3) RGB or (F, H, W) grey frames, got {tuple(frames.shape)}")
 
@@ -51,13 +45,12 @@ def encode_frames(frames):
     the 2 F offsets and lengths, then the packed compressed bytes; no raw frame."""
     out, offsets, lengths = encode_streams(frames)
     F, H, W = frames.shape[:3]
-    where = torch.stack([offsets, lengths]).cpu().tolist()
-    total = where[0][-1] + where[1][-1]
-    packed = out[:total].cpu().numpy().tobytes()
+    spans, total = _encode.fetch_spans(offsets, lengths)
+    packed = _encode.fetch_bytes(out, total)
     ihdr = _chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 2 if frames.ndim == 4 else 0, 0, 0, 0))
     iend = _chunk(b"IEND", b"")
     files = []
-    for o, n in zip(*where):
+    for o, n in spans:
         body = packed[o:o + n]
         files.append(b"".join((_SIG, ihdr, struct.pack(">I", n), b"IDAT", body,
                                struct.pack(">I", zlib.crc32(body, zlib.crc32(b"IDAT")) & 0xffffffff), iend)))
@@ -66,10 +59,4 @@ def encode_frames(frames):
 
 def write_frames(paths, frames):
     """Writes frame i to paths[i]."""
-    paths = list(paths)
-    _check(frames)
-    if len(paths) != frames.shape[0]:
-        raise ValueError(f"write_frames: {len(paths)} paths for {frames.shape[0]} frames")
-    for path, data in zip(paths, encode_frames(frames)):
-        with open(path, "wb") as f:
-            f.write(data)
+    _encode.write_files(paths, encode_frames(frames))

@@ -166,6 +166,57 @@ def test_single_symbol_segment():
         _check(_encode(img[None]), img[None])
 
 
+# The inputs of test_streams_equal_the_recorded_ones, the smallest that reach each path of the encoder: one pixel; a
+# column; two segments with the boundary inside a row (twice, so that one shape has a batch); the stored fallback;
+# alphabets of one literal and one length symbol; runs of 2, 3, 258, 259 and 260; segments of one run each.
+PIN_CASES = {
+    "1x1_rgb": SHAPE_CASES["1x1_rgb"],
+    "1x1_grey": SHAPE_CASES["1x1_grey"],
+    "7x1_grey": SHAPE_CASES["7x1_grey"],
+    "67x173_rgb_blobs": SHAPE_CASES["67x173_rgb_blobs"],
+    "67x173_rgb_blobs_white": _blobs(67, 173, 0.9, white=True),
+    "40x50_rgb_noise": _rng(41).integers(0, 256, (40, 50, 3), dtype=np.uint8),
+    "1x258_zeros": np.zeros((1, 258), np.uint8),
+    "1x259_zeros": np.zeros((1, 259), np.uint8),
+    "runs": _runs_image(),
+    "64x1024_zeros": np.zeros((64, 1024), np.uint8),
+}
+PIN_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "png_encode_streams.npz")
+
+
+def pin_streams(frames):
+    """png_gpu.encode_streams on the host: (the packed bytes up to the last stream's end, offsets, lengths)."""
+    from deformgs import png_gpu
+    packed, offsets, lengths = png_gpu.encode_streams(torch.from_numpy(np.ascontiguousarray(frames)).cuda())
+    offsets, lengths = offsets.cpu().numpy(), lengths.cpu().numpy()
+    return packed[:int(offsets[-1] + lengths[-1])].cpu().numpy(), offsets, lengths
+
+
+def test_streams_equal_the_recorded_ones():
+    """The zlib streams, byte for byte, against those the encoder of the recorded parent revision wrote for the
+    same inputs (tests/golden/make_golden_png_encode.py): a change that is meant to leave the bytes alone is held to
+    it. Then every shape with more than one case as one batch: its frames' streams are the recorded ones, back to
+    back."""
+    gold = np.load(PIN_PATH)
+    assert sorted(str(c) for c in gold["cases"]) == sorted(PIN_CASES)
+    by_shape = {}
+    for name, img in PIN_CASES.items():
+        packed, offsets, lengths = pin_streams(img[None])
+        assert offsets.dtype == lengths.dtype == np.int64
+        assert offsets.tolist() == gold[f"{name}_offsets"].tolist() == [0], name
+        assert lengths.tolist() == gold[f"{name}_lengths"].tolist(), name
+        assert packed.tobytes() == gold[f"{name}_packed"].tobytes(), name
+        by_shape.setdefault(img.shape, []).append(name)
+    batches = [names for names in by_shape.values() if len(names) > 1]
+    assert batches
+    for names in batches:
+        packed, offsets, lengths = pin_streams(np.stack([PIN_CASES[n] for n in names]))
+        want = [gold[f"{n}_packed"].tobytes() for n in names]
+        assert lengths.tolist() == [len(w) for w in want], names
+        assert offsets.tolist() == np.concatenate([[0], np.cumsum(lengths)[:-1]]).tolist(), names
+        assert packed.tobytes() == b"".join(want), names
+
+
 def test_batch_of_five_and_reproducible():
     frames = np.stack([_blobs(67, 173, 0.1), _blobs(67, 173, 0.9, white=True),
                        _rng(31).integers(0, 256, (67, 173, 3), dtype=np.uint8), np.full((67, 173, 3), 9, np.uint8),

@@ -1,14 +1,19 @@
 #!/usr/bin/env python3
-"""Bitwise comparison of two builds of libdgs_hip.so on the fused MLP or on the SSIM kernels (a kernel
-restructuring that keeps every summation order must reproduce the previous build's bits).
+"""Bitwise comparison of two builds of libdgs_hip.so on the fused MLP, on the SSIM kernels or on the image codecs
+(a kernel restructuring that keeps every summation order must reproduce the previous build's bits).
   python3 tools/lib_bitwise.py dump OUT.npz      (with DGS_LIB=... selecting the build)
   python3 tools/lib_bitwise.py dump_ssim OUT.npz
+  python3 tools/lib_bitwise.py dump_codecs OUT.npz
   python3 tools/lib_bitwise.py cmp A.npz B.npz
 dump runs DeformNetworkBaseline forward + backward (blender and non-blender; frame-uniform t and
 per-point t; ragged N), then the same forward under torch.no_grad (the inference kernels), and stores
 the outputs and every parameter gradient. dump_ssim stores l1_ssim_loss's three outputs and dL/dimg
 (upstream gradient 1 and 3) and image_metrics' raw (F, 3 + 10 C) output, NaN slots included, on seeded
-images. cmp compares bytes, not values."""
+images. dump_codecs stores the packed streams, offsets and lengths of png_gpu.encode_streams and of
+jpeg_gpu.encode_streams (with its flags; three samplings, qualities 75 / 90 / 100, and once a capacity that the
+frames exceed) on seeded frames: 256x256 discs, noise, constants, odd sizes, two 800x800 renders of the synthetic
+scene; and the uint8 output of the device JPEG decoder on the files of tests/golden/jpeg_ingest.npz. cmp compares
+bytes, not values."""
 import os
 import sys
 
@@ -78,6 +83,56 @@ def dump_ssim(path):
     print(f"dumped {len(out)} arrays to {path}")
 
 
+def dump_codecs(path):
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from deformgs import ingest, jpeg_gpu, png_gpu
+    from encode_time import render
+    from png_fixtures import disc_image
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(0)
+
+    def discs(h, w, t, bg):
+        d = disc_image(w, h, t, n_discs=5, seed=3).astype(np.int32)
+        return ((d[:, :, :3] * d[:, :, 3:] + bg * (255 - d[:, :, 3:]) + 127) // 255).astype(np.uint8)
+
+    rgb = {"discs_256": np.stack([discs(256, 256, 0.2, 0), discs(256, 256, 0.7, 255)]),
+           "noise_120x160": rng.integers(0, 256, (1, 120, 160, 3), dtype=np.uint8),
+           "const_256": np.stack([np.full((256, 256, 3), 77, np.uint8), np.zeros((256, 256, 3), np.uint8)]),
+           "mixed_67x173": np.stack([discs(67, 173, 0.1, 0), rng.integers(0, 256, (67, 173, 3), dtype=np.uint8),
+                                     np.full((67, 173, 3), 9, np.uint8)]),
+           "one_pixel": rng.integers(0, 256, (1, 1, 1, 3), dtype=np.uint8),
+           "render_800": render(2, 800, 100000, dev).cpu().numpy()}
+    grey = {"grey_discs_250x300": discs(250, 300, 0.6, 0)[None, :, :, 1], "grey_zeros_64x1024": np.zeros((1, 64, 1024), np.uint8),
+            "grey_7x1": rng.integers(0, 256, (1, 7, 1), dtype=np.uint8)}
+    out = {}
+
+    def store(key, packed, offsets, lengths, flags=None):
+        where = torch.stack([offsets, lengths]).cpu().numpy()
+        end = min(int(where[0, -1] + where[1, -1]), packed.numel())
+        if flags is not None:  # a frame that did not fit was not written: its bytes are whatever the buffer held
+            out[key + "/flags"] = flags.cpu().numpy()
+            ok = np.flatnonzero(out[key + "/flags"] == 0)
+            end = int(where[0, ok[-1]] + where[1, ok[-1]]) if ok.size else 0
+        out[key + "/packed"], out[key + "/offsets"], out[key + "/lengths"] = packed[:end].cpu().numpy(), where[0], where[1]
+
+    for name, a in {**rgb, **grey}.items():
+        store("png_" + name, *png_gpu.encode_streams(torch.from_numpy(np.ascontiguousarray(a)).to(dev)))
+    for name, a in rgb.items():
+        frames = torch.from_numpy(a).to(dev)
+        for sub in jpeg_gpu.SAMPLING:
+            for q in (75, 90, 100):
+                store(f"jpeg_{name}_{sub}_q{q}", *jpeg_gpu.encode_streams(frames, q, sub, capacity=4 * a.size + 4096))
+    a = rgb["mixed_67x173"]  # the noise frame does not fit: flagged, and only the frame before it is written
+    store("jpeg_mixed_67x173_4:2:0_q90_cap8000", *jpeg_gpu.encode_streams(torch.from_numpy(a).to(dev), 90, "4:2:0", capacity=8000))
+    gold = np.load(os.path.join(ROOT, "tests", "golden", "jpeg_ingest.npz"))
+    for c in gold["cases"]:
+        out[f"decode_{c}"] = ingest.ingest_images([gold[f"{c}_jpg"].tobytes()], False, device=dev, return_uint8=True)[1][0].cpu().numpy()
+    np.savez(path, **out)
+    print(f"dumped {len(out)} arrays to {path}")
+
+
 def cmp(pa, pb):
     a, b = np.load(pa), np.load(pb)
     assert sorted(a.files) == sorted(b.files), "different keys"
@@ -90,7 +145,7 @@ def cmp(pa, pb):
 
 
 if __name__ == "__main__":
-    if sys.argv[1] in ("dump", "dump_ssim"):
-        {"dump": dump, "dump_ssim": dump_ssim}[sys.argv[1]](sys.argv[2])
+    if sys.argv[1] in ("dump", "dump_ssim", "dump_codecs"):
+        {"dump": dump, "dump_ssim": dump_ssim, "dump_codecs": dump_codecs}[sys.argv[1]](sys.argv[2])
     else:
         sys.exit(cmp(sys.argv[2], sys.argv[3]))
