@@ -8,13 +8,15 @@ from deformgs.synthetic import synth_camera, synth_gaussians
 from oracle.raster import OracleRaster, make_settings
 
 
-def scene(N, H, W, seed=0, cam_index=0, scale_boost=0.0, device="cpu", bg=(0.0, 0.0, 0.0), sh_degree=3):
+def scene(N, H, W, seed=0, cam_index=0, scale_boost=0.0, device="cpu", bg=(0.0, 0.0, 0.0), sh_degree=3, sh_coeffs=16):
+    """sh_coeffs: the SH coefficients per Gaussian (M <= 16: the first M rows of the degree-3 set, so
+    scenes of different M share every other input)."""
     g = synth_gaussians(N, seed=seed, device="cpu")
     g["scaling"] = g["scaling"] + scale_boost
     cam = synth_camera(W, H, index=cam_index, device="cpu")
     inputs = dict(
         means3D=g["xyz"],
-        shs=torch.cat([g["features_dc"], g["features_rest"]], 1),
+        shs=torch.cat([g["features_dc"], g["features_rest"]], 1)[:, :sh_coeffs].contiguous(),
         opacities=torch.sigmoid(g["opacity"]),
         scales=torch.exp(g["scaling"]),
         rotations=torch.nn.functional.normalize(g["rotation"]),

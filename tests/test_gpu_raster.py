@@ -7,12 +7,14 @@ order and a Gaussian whose alpha sits exactly on the 1/255 or T<1e-4 thresholds 
 fp32 implementations (exp differs by an ulp). Parity of the rasterizer is UNPINNED by the reference
 (no CUDA op, no fixture); the oracle is the spec (oracle/raster_ref.c header).
 """
+import functools
+
 import numpy as np
 import pytest
 import torch
 
-from helpers import (check_gaussian_grad, check_image, check_integer_outputs, frac_close, oracle_run, rel_err, scene,
-                     settings_for_gpu, tail_sets, write_stats)
+from helpers import (ASSERT_EPS, check_gaussian_grad, check_image, check_integer_outputs, frac_close, integer_ambiguity,
+                     oracle_run, rel_err, scene, settings_for_gpu, tail_sets, write_stats)
 
 pytestmark = pytest.mark.gpu
 
@@ -35,11 +37,33 @@ def binning(request):
     lib.dgs_debug_set_binning(0)
 
 
-def _run_gpu(inputs, rs, dcolor, ddepth, use_cov=False, use_colors=False, requires=True):
+def _misaligned(x):
+    """A contiguous copy of x on the GPU that starts one float into a larger buffer."""
+    buf = torch.empty(x.numel() + 4, dtype=torch.float32, device="cuda")
+    v = buf[1:1 + x.numel()].view(x.shape)
+    v.copy_(x)
+    assert v.is_contiguous() and v.data_ptr() % 16 == 4
+    return v
+
+
+def _poison_free_blocks(shapes):
+    """NaN-filled tensors of the given shapes, allocated and freed: the caching allocator is then likely
+    to hand these blocks to the next allocations of the same sizes (a gradient the backward leaves
+    partly unwritten shows NaN instead of a stale zero)."""
+    blocks = [torch.full(s, float("nan"), device="cuda") for s in shapes]
+    del blocks
+
+
+def _run_gpu(inputs, rs, dcolor, ddepth, use_cov=False, use_colors=False, requires=True, misalign_shs=False,
+             poison=False):
     from diff_gaussian_rasterization import GaussianRasterizer
     dev = "cuda"
     t = {k: v.to(dev).clone().requires_grad_(requires) for k, v in inputs.items()}
     N = t["means3D"].shape[0]
+    if misalign_shs:
+        t["shs"] = _misaligned(inputs["shs"]).requires_grad_(requires)
+    elif "shs" in t:
+        assert t["shs"].data_ptr() % 16 == 0
     m2 = torch.zeros((N, 3), device=dev, requires_grad=True)
     m2d = torch.zeros((N, 3), device=dev, requires_grad=True)
     r = GaussianRasterizer(settings_for_gpu(rs))
@@ -58,6 +82,8 @@ def _run_gpu(inputs, rs, dcolor, ddepth, use_cov=False, use_colors=False, requir
     loss = (color * torch.tensor(dcolor, device=dev)).sum()
     if ddepth is not None:
         loss = loss + (depth * torch.tensor(ddepth, device=dev)).sum()
+    if poison:  # the sizes of the raster backward's gradient allocations
+        _poison_free_blocks([tuple(t["shs"].shape)] + [(N, 3)] * 4 + [(N, 4), (N, 1)])
     loss.backward()
     grads = {k: v.grad.cpu().numpy() for k, v in t.items()}
     grads["means2D"] = m2.grad.cpu().numpy()
@@ -127,6 +153,103 @@ def test_raster_sh_degrees():
         color, radii, depth, grads = _run_gpu(inputs, rs, dcolor, None)
         _check(o, g, color, radii, depth, grads, [("shs", "shs"), ("means3D", "means3D")], nr=_run_gpu.num_rendered,
                tag=f"raster_sh_degree{deg}")
+
+
+# ---- SH rows the preprocess kernels read and write per thread (k_preprocess<false>, k_preprocess_bwd<false>):
+# M < 16 (models of sh_degree 0 / 1 / 2), or M = 16 in a tensor that is not 16-byte aligned ----
+LOW_SH = [
+    # M, D, N, H, W; D < the maximum of M: the backward zeroes the coefficients kmax .. M
+    (1, 0, 800, 64, 64), (4, 1, 800, 64, 64), (4, 0, 800, 64, 64), (9, 2, 800, 64, 64), (9, 1, 800, 64, 64),
+    (9, 0, 800, 64, 64), (16, 3, 800, 64, 64), (16, 1, 800, 64, 64),  # M = 16: misaligned SH tensor
+    (9, 1, 1000, 61, 83),                                             # ragged image
+]
+_ALL_GRADS = [("means3D", "means3D"), ("shs", "shs"), ("opacities", "opacities"), ("scales", "scales"),
+              ("rotations", "rotations"), ("means2D", "means2D"), ("means2D_densify", "means2D_densify")]
+
+
+@functools.lru_cache(maxsize=None)
+def _low_sh_scene(M, D, N, H, W):
+    """The scene of test_raster_sh_degrees with M coefficients and one Gaussian in ten behind the camera
+    (culled: its SH gradient row is zeroed by the !vis loop), and its oracle result, computed once."""
+    inputs, rs, _ = scene(N, H, W, cam_index=1, scale_boost=0.8, sh_degree=D, sh_coeffs=M)
+    behind = (torch.arange(N) % 10 == 3)[:, None]
+    inputs["means3D"] = torch.where(behind, rs["campos"][None] * 1.5 + 0.01 * inputs["means3D"], inputs["means3D"])
+    rng = np.random.default_rng(100 * M + D)
+    dcolor = rng.standard_normal((3, H, W)).astype(np.float32)
+    ddepth = rng.standard_normal((1, H, W)).astype(np.float32) * 0.1
+    o, g = oracle_run(inputs, rs, dcolor, ddepth)
+    return inputs, rs, dcolor, ddepth, o, g
+
+
+def _low_sh_scene_sanity(o):
+    """The scene exercises what the test is about (oracle side, no GPU): enough drawn and enough culled
+    Gaussians, pairs to blend, and few Gaussians excused by a near-threshold decision."""
+    assert int((o.radii > 0).sum()) >= 300 and int((o.radii == 0).sum()) >= 50 and o.num_rendered > 0
+    gflag = tail_sets(o, integer_ambiguity(o))[ASSERT_EPS][0]
+    assert gflag.mean() <= 0.05, gflag.mean()
+
+
+@pytest.mark.parametrize("M,D,N,H,W", LOW_SH, ids=[f"M{c[0]}-D{c[1]}-{c[2]}x{c[3]}x{c[4]}" for c in LOW_SH])
+def test_raster_low_sh(M, D, N, H, W):
+    """Unstaged SH rows vs the oracle: every check of test_raster_sh_scale_rot; the SH gradient rows of
+    culled Gaussians and the coefficients above the active degree are exactly zero (the gradient buffer
+    is likely a block that held NaNs just before the backward)."""
+    inputs, rs, dcolor, ddepth, o, g = _low_sh_scene(M, D, N, H, W)
+    _low_sh_scene_sanity(o)
+    assert tuple(inputs["shs"].shape) == (N, M, 3) and M >= (D + 1) ** 2
+    color, radii, depth, grads = _run_gpu(inputs, rs, dcolor, ddepth, misalign_shs=M == 16, poison=True)
+    tag = f"raster_low_sh[{M},{D}]" if (N, H, W) == (800, 64, 64) else f"raster_low_sh[{M},{D},{N}x{H}x{W}]"
+    _check(o, g, color, radii, depth, grads, _ALL_GRADS, nr=_run_gpu.num_rendered, tag=tag)
+    dsh = grads["shs"]
+    kmax = (D + 1) ** 2
+    culled = radii == 0
+    assert dsh.shape == (N, M, 3) and int(culled.sum()) >= 50
+    assert not np.isnan(dsh).any()
+    assert (dsh[culled] == 0).all(), "SH gradient rows of culled Gaussians must be written as zeros"
+    assert (dsh[:, kmax:] == 0).all(), "SH gradient coefficients above the active degree must be zeros"
+    assert (np.abs(dsh[~culled][:, :kmax]).max(axis=(1, 2)) > 0).mean() > 0.5
+
+
+def test_raster_misaligned_sh_equals_aligned():
+    """M = 16 at degree 3, aligned (SH rows staged through LDS) vs one float off 16-byte alignment (read
+    and written per thread): both kernels state the same arithmetic, so images, depth and radii are
+    bitwise equal and the gradients equal up to the float atomics' arrival order (1e-5 of each
+    tensor's max)."""
+    inputs, rs, dcolor, ddepth, o, g = _low_sh_scene(16, 3, 800, 64, 64)
+    a = _run_gpu(inputs, rs, dcolor, ddepth) + (_run_gpu.num_rendered,)
+    b = _run_gpu(inputs, rs, dcolor, ddepth, misalign_shs=True) + (_run_gpu.num_rendered,)
+    assert a[4] == b[4] > 0
+    for x, y in zip(a[:3], b[:3]):
+        np.testing.assert_array_equal(x, y)
+    for k in a[3]:
+        scale = max(float(np.abs(a[3][k]).max()), 1e-30)
+        assert float(np.abs(a[3][k] - b[3][k]).max()) / scale < 1e-5, k
+
+
+@pytest.mark.parametrize("M,D", [(4, 2), (9, 3), (16, 4)])
+def test_raster_rejects_degree_beyond_coefficients(M, D):
+    """dgs_raster_forward refuses M < (D + 1)^2 and D > 3 as an argument error, before any launch (the
+    preprocess kernel would read past the SH rows)."""
+    from deformgs import _lib
+    from diff_gaussian_rasterization import GaussianRasterizer
+    lib = _lib.load()
+    inputs, rs, _ = scene(64, 32, 32, sh_degree=D, sh_coeffs=M)
+    t = {k: v.cuda() for k, v in inputs.items()}
+    r = GaussianRasterizer(settings_for_gpu(rs))
+    lib.dgs_timing_enable(1)
+    try:
+        before = lib.dgs_timing_launches(b"preprocess_fwd")
+        with pytest.raises(ValueError, match="SH degree"):
+            r(means3D=t["means3D"], means2D=torch.zeros((64, 3), device="cuda"), opacities=t["opacities"],
+              shs=t["shs"], scales=t["scales"], rotations=t["rotations"])
+        assert lib.dgs_timing_launches(b"preprocess_fwd") == before
+        # the counter does see a launch: the same call with the degree the coefficients allow
+        ok = GaussianRasterizer(settings_for_gpu(dict(rs, sh_degree=min(D, 3) - 1)))
+        ok(means3D=t["means3D"], means2D=torch.zeros((64, 3), device="cuda"), opacities=t["opacities"],
+           shs=t["shs"], scales=t["scales"], rotations=t["rotations"])
+        assert lib.dgs_timing_launches(b"preprocess_fwd") == before + 1
+    finally:
+        lib.dgs_timing_enable(0)
 
 
 def test_raster_edge_cases():
