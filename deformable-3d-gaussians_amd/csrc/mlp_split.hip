@@ -72,6 +72,7 @@
 #include "mlp_split_bwd.h"
 #include "mlp_split_dw.h"
 #include "mlp_split_pack.h"
+#include "mlp_active.h"
 
 namespace dgs {
 namespace mlps {
@@ -96,15 +97,6 @@ static WPlan split_wplan(const Flags &F, int target = 256) {
 
 static size_t padded_points(int N) { return (size_t)div_up(N, BM) * BM; }
 
-// Block decomposition of the fused forward / dX kernels (one 147 KB workgroup per CU): when the last
-// round of 64-point blocks would occupy at most a quarter of the CUs, those blocks run as four times
-// as many 16-point blocks instead (fwd_block / bwd_block NQB = 1), so the sparse last round ends in
-// roughly a third of a full block's time (the A stream, not the MFMAs, bounds a 16-point block).
-// DGS_MLP_NO_TAIL=1 keeps 64-point blocks throughout. Mask slots: one per block (<= nb + 3 min(nb, 128)).
-constexpr int TAIL_MAX_LAST = 128;
-struct Blocks {
-    int nfull, ntail;
-};
 static int cu_count() {
     static std::mutex mu;
     static std::map<int, int> cache;
@@ -135,15 +127,12 @@ static int reserved_cus() {
     return v;
 }
 static int mlp_cus() { return std::max(1, cu_count() - reserved_cus()); }
-static Blocks block_split(int N) {
-    const int nb = div_up(N, BM);
+// the CUs split_blocks spreads a sparse last round over (0: DGS_MLP_NO_TAIL=1 keeps 64-point blocks)
+static int tail_cus() {
     static const bool off = env_starts("DGS_MLP_NO_TAIL", '1');
-    if (off || nb == 0) return {nb, 0};
-    const int ncu = mlp_cus();
-    const int rounds = div_up(nb, ncu), last = nb - ncu * (rounds - 1);
-    if (rounds < 2 || last > TAIL_MAX_LAST || 4 * last > ncu) return {nb, 0};
-    return {nb - last, 4 * last};
+    return off ? 0 : mlp_cus();
 }
+static Blocks block_split(int N) { return split_blocks(N, tail_cus()); }
 // Block-queue counters of the persistent k_fwd / k_bwd, one zeroed pair per (device, stream, kernel)
 // (two launches in flight on two streams must not share one). DGS_MLP_STATIC=1: one launch block per
 // block, no queue (A/B).
@@ -197,9 +186,6 @@ static int dw_mode() {
     static const int m = env_starts("DGS_MLP_SPLIT_DW", '0') ? 0 : 3;
     return m;
 }
-static int dw_split_once(const Flags &F, size_t Ns, const float *dz, const float *saved, float *slabs,
-                         float *const *grads, hipStream_t stream);
-
 size_t scratch_floats(int flags, int N) {
     const Flags F = make_flags(flags);
     const size_t slabs = std::max((size_t)split_wplan(F).nblocks * SLAB, mlp::dw_fp32_slab_floats(flags));
@@ -240,12 +226,18 @@ int pack(int flags, const float *const *params, float *packed, hipStream_t strea
 static void fwd_args(const Plan &P, int flags, int N, const float *xyz, const float *t, const float *packed, float *out,
                      float *saved, FwdArgs &a, hipStream_t stream);
 
+// nosave: the training forward (saved given, frame-uniform t) with its saved-row and mask stores compiled
+// out (k_fwd8_nosave); `saved` still receives k_timenet's constants, which backward_active() reads
 int forward(int flags, int N, const float *xyz, const float *t, const float *packed, float *out, float *saved,
-            hipStream_t stream) {
+            hipStream_t stream, bool nosave) {
     const Plan P = make_plan(flags);
     FwdArgs a{};
     fwd_args(P, flags, N, xyz, t, packed, out, saved, a, stream);
     const int grid = persistent_grid(a.nblk, a.queue);
+    if (nosave && !(saved && P.F.uniform_t)) {
+        set_error("dgs_deform_forward: DGS_MLP_NO_SAVE needs DGS_MLP_UNIFORM_T and the saved buffer");
+        return DGS_ERR_ARGS;
+    }
     if (P.F.blender && (saved || P.F.uniform_t)) {
         // the folded biases (uniform t) are needed without saved activations too (inference)
         if (!a.tc) {
@@ -257,7 +249,9 @@ int forward(int flags, int N, const float *xyz, const float *t, const float *pac
     {
         ScopedTimer tm("mlp_fwd", stream);  // k_fwd only: the class's FLOP count is the trunk's + heads'
         const bool fold = P.F.uniform_t;  // t_emb folded into the biases (a.tc is set above)
-        if (saved && fold)  // every training step: 8 waves of two n-tiles (DESIGN.md §"k_fwd8")
+        if (nosave)
+            hipLaunchKernelGGL(k_fwd8_nosave, dim3(grid), dim3(NTHR8), 0, stream, a);
+        else if (saved && fold)  // every training step: 8 waves of two n-tiles (DESIGN.md §"k_fwd8")
             hipLaunchKernelGGL(k_fwd8, dim3(grid), dim3(NTHR8), 0, stream, a);
         else if (saved)
             hipLaunchKernelGGL((k_fwd<true, false>), dim3(grid), dim3(NTHR), 0, stream, a);
@@ -276,9 +270,9 @@ int forward(int flags, int N, const float *xyz, const float *t, const float *pac
 // the map double-indirection serialised the timenet's loads and its registers lowered the pack's
 // occupancy), so the two launches stay.
 int pack_forward(int flags, const float *const *params, int N, const float *xyz, const float *t, float *packed,
-                 float *out, float *saved, hipStream_t stream) {
+                 float *out, float *saved, hipStream_t stream, bool nosave) {
     if (int rc = pack(flags, params, packed, stream)) return rc;
-    return forward(flags, N, xyz, t, packed, out, saved, stream);
+    return forward(flags, N, xyz, t, packed, out, saved, stream, nosave);
 }
 
 static void fwd_args(const Plan &P, int flags, int N, const float *xyz, const float *t, const float *packed, float *out,
@@ -299,13 +293,19 @@ static void fwd_args(const Plan &P, int flags, int N, const float *xyz, const fl
     const int nblk = bs.nfull + bs.ntail;
     a.nblk = nblk;
     a.queue = nblk > 0 ? block_queue(stream, 0) : nullptr;
+    a.n_dev = nullptr;
+    a.ncu = tail_cus();
     a.tc = nullptr;
     if (P.F.blender && (saved || P.F.uniform_t))
         a.tc = saved ? saved + (size_t)P.F.nsaved * a.Ns + mask_words(P.F, a.Ns) : timenet_scratch(stream);
 }
 
-int backward(int flags, int N, const float *packed, const float *saved, const float *dout, float *scratch,
-             float *const *grads, hipStream_t stream) {
+static int dw_split_once(const Flags &F, size_t Ns, int N, const int *n_dev, const float *dz, const float *saved,
+                         float *slabs, float *const *grads, hipStream_t stream);
+
+// n_dev: the point count in device memory (<= N: the active set) or nullptr: the N rows of dout
+static int backward_n(int flags, int N, const int *n_dev, const float *packed, const float *saved, const float *dout,
+                      float *scratch, float *const *grads, hipStream_t stream) {
     const Plan P = make_plan(flags);
     const Flags &F = P.F;
     const size_t Ns = padded_points(N);
@@ -323,6 +323,8 @@ int backward(int flags, int N, const float *packed, const float *saved, const fl
     const int nblk = bs.nfull + bs.ntail;
     b.nblk = nblk;
     b.queue = nblk > 0 ? block_queue(stream, 1) : nullptr;
+    b.n_dev = n_dev;
+    b.ncu = tail_cus();
     const int grid = persistent_grid(nblk, b.queue);
     {
         ScopedTimer tm("mlp_bwd", stream);
@@ -336,10 +338,10 @@ int backward(int flags, int N, const float *packed, const float *saved, const fl
     }
     DGS_LAUNCH_CHECK("k_bwd", false, stream);
     int rc;
-    if (dw_mode() == 0)
+    if (dw_mode() == 0 && !n_dev)
         rc = mlp::dw_fp32(F, Ns, dz, saved, slabs, grads, stream);
     else
-        rc = dw_split_once(F, Ns, dz, saved, slabs, grads, stream);
+        rc = dw_split_once(F, Ns, N, n_dev, dz, saved, slabs, grads, stream);
     if (rc != DGS_OK || !F.uniform_t) return rc;
     TGradArgs g{};
     g.fp = packed + P.img_floats();
@@ -360,9 +362,14 @@ int backward(int flags, int N, const float *packed, const float *saved, const fl
 // dW launches handed to the fp32 k_dw because a 256-row operand exceeds k_dws's 32-bit byte offsets
 // (N > ~2.1 M points; dgs_debug_dw_fallbacks)
 static std::atomic<long long> g_dw_fallbacks{0};
-static int dw_split_once(const Flags &F, size_t Ns, const float *dz, const float *saved, float *slabs,
-                         float *const *grads, hipStream_t stream) {
-    if ((size_t)WT * Ns * 4 >= 0x7fffffffull) {  // 32-bit byte offsets of a 256-row operand
+static bool dws_offsets_fit(size_t Ns) { return (size_t)WT * Ns * 4 < 0x7fffffffull; }
+static int dw_split_once(const Flags &F, size_t Ns, int N, const int *n_dev, const float *dz, const float *saved,
+                         float *slabs, float *const *grads, hipStream_t stream) {
+    if (!dws_offsets_fit(Ns)) {  // 32-bit byte offsets of a 256-row operand
+        if (n_dev) {  // active_supported() keeps such launches on the full path
+            set_error("dgs_deform_backward_active: too many points for k_dws");
+            return DGS_ERR_ARGS;
+        }
         g_dw_fallbacks.fetch_add(1);
         return mlp::dw_fp32(F, Ns, dz, saved, slabs, grads, stream);
     }
@@ -379,10 +386,92 @@ static int dw_split_once(const Flags &F, size_t Ns, const float *dz, const float
     {
         if (int rc = ensure_dynamic_lds((const void *)k_dws, S_LDS)) return rc;
         ScopedTimer tm("mlp_dw", stream);
-        hipLaunchKernelGGL(k_dws, dim3(W.nblocks), dim3(DW_THREADS), S_LDS, stream, W.jobs, Ns, dz, saved, slabs);
+        hipLaunchKernelGGL(k_dws, dim3(W.nblocks), dim3(DW_THREADS), S_LDS, stream, W.jobs, Ns, N, n_dev, dz, saved,
+                           slabs);
     }
     DGS_LAUNCH_CHECK("k_dws", false, stream);
     return launch_dw_reduce(F, W, slabs, grads, stream);
+}
+
+int backward(int flags, int N, const float *packed, const float *saved, const float *dout, float *scratch,
+             float *const *grads, hipStream_t stream) {
+    return backward_n(flags, N, nullptr, packed, saved, dout, scratch, grads, stream);
+}
+
+// ---- the active set (mlp_active.h). Scratch: M | the count kernel's per-workgroup counts | xyz_c | dout_c ----
+struct ActiveBufs {
+    int *m, *counts;
+    float *xyz_c, *dout_c;
+    size_t total;
+};
+static ActiveBufs active_bufs(const Flags &F, int N, float *base) {
+    auto pad4 = [](size_t n) { return (n + 3) / 4 * 4; };
+    ActiveBufs b{};
+    size_t o = 4;
+    b.m = reinterpret_cast<int *>(base);
+    b.counts = reinterpret_cast<int *>(base + o);
+    o += pad4(div_up(std::max(N, 1), ACT_ROWS));
+    b.xyz_c = base + o;
+    o += pad4((size_t)3 * N);
+    b.dout_c = base + o;
+    o += pad4((size_t)F.nout * N);
+    b.total = o;
+    return b;
+}
+size_t active_floats(int flags, int N) { return active_bufs(make_flags(flags), N, nullptr).total; }
+
+// the recompute path runs the kernels that take a device point count: k_fwd8 / k_bwd8 (a frame-uniform
+// t) and the split k_dws within its 32-bit offsets
+bool active_supported(int flags, int N) {
+    return make_flags(flags).uniform_t && dw_mode() == 3 && dws_offsets_fit(padded_points(N));
+}
+
+static ActiveArgs active_args(const Flags &F, int N, const float *xyz, const float *dout, const ActiveBufs &B,
+                              uint32_t *m_host) {
+    ActiveArgs g{};
+    g.N = N; g.nout = F.nout; g.xyz = xyz; g.dout = dout;
+    g.xyz_c = B.xyz_c; g.dout_c = B.dout_c; g.counts = B.counts; g.m_dev = B.m; g.m_host = m_host;
+    return g;
+}
+
+// M only (a step on the full path: the active fraction is still measured)
+int active_count(int flags, int N, const float *dout, float *active, uint32_t *m_host, hipStream_t stream) {
+    const Flags F = make_flags(flags);
+    const ActiveArgs g = active_args(F, N, nullptr, dout, active_bufs(F, N, active), m_host);
+    ScopedTimer tm("mlp_active", stream);
+    hipLaunchKernelGGL(k_active_count, dim3(div_up(N, ACT_ROWS)), dim3(ACT_ROWS), 0, stream, g);
+    hipLaunchKernelGGL(k_active_gather, dim3(1), dim3(ACT_ROWS), 0, stream, g, 0);
+    DGS_LAUNCH_CHECK("k_active_count", false, stream);
+    return DGS_OK;
+}
+
+// The backward of a forward(nosave) launch with the same packed / saved buffers: compact the rows of
+// dout with a nonzero element, rerun the saving forward on their xyz (k_timenet's constants of the
+// first forward are in `saved`; no output rows), then the dX chain and dW on those M points.
+int backward_active(int flags, int N, const float *xyz, const float *packed, float *saved, const float *dout,
+                    float *scratch, float *active, uint32_t *m_host, float *const *grads, hipStream_t stream) {
+    const Plan P = make_plan(flags);
+    if (!active_supported(flags, N)) {
+        set_error("dgs_deform_backward_active: not available for these flags / this size (dgs_deform_active_supported)");
+        return DGS_ERR_ARGS;
+    }
+    const ActiveBufs B = active_bufs(P.F, N, active);
+    const ActiveArgs g = active_args(P.F, N, xyz, dout, B, m_host);
+    {
+        ScopedTimer tm("mlp_active", stream);
+        hipLaunchKernelGGL(k_active_count, dim3(div_up(N, ACT_ROWS)), dim3(ACT_ROWS), 0, stream, g);
+        hipLaunchKernelGGL(k_active_gather, dim3(div_up(N, ACT_ROWS)), dim3(ACT_ROWS), 0, stream, g, 1);
+    }
+    DGS_LAUNCH_CHECK("k_active_gather", false, stream);
+    FwdArgs a{};
+    fwd_args(P, flags, N, B.xyz_c, nullptr, packed, nullptr, saved, a, stream);
+    a.n_dev = B.m;
+    {
+        ScopedTimer tm("mlp_fwd_active", stream);
+        hipLaunchKernelGGL(k_fwd8, dim3(persistent_grid(a.nblk, a.queue)), dim3(NTHR8), 0, stream, a);
+    }
+    DGS_LAUNCH_CHECK("k_fwd8", false, stream);
+    return backward_n(flags, N, B.m, packed, saved, B.dout_c, scratch, grads, stream);
 }
 
 }  // namespace mlps
@@ -463,8 +552,13 @@ extern "C" int dgs_deform_forward(int flags, int N, const float *xyz, const floa
         return DGS_ERR_ARGS;
     }
     if (N == 0) return DGS_OK;
+    if (exact_fp32(flags) && (flags & DGS_MLP_NO_SAVE)) {
+        set_error("dgs_deform_forward: DGS_MLP_NO_SAVE is the split path's");
+        return DGS_ERR_ARGS;
+    }
     return exact_fp32(flags) ? mlp::forward(net_flags(flags), N, xyz, t, packed, out, saved, stream)
-                             : mlps::forward(net_flags(flags), N, xyz, t, packed, out, saved, stream);
+                             : mlps::forward(net_flags(flags), N, xyz, t, packed, out, saved, stream,
+                                             (flags & DGS_MLP_NO_SAVE) != 0);
 }
 
 extern "C" int dgs_deform_pack_forward(int flags, const float *const *params, int N, const float *xyz, const float *t,
@@ -478,7 +572,8 @@ extern "C" int dgs_deform_pack_forward(int flags, const float *const *params, in
         if (int rc = dgs_deform_pack(flags, params, packed, stream_)) return rc;
         return dgs_deform_forward(flags, N, xyz, t, packed, out, saved, stream_);
     }
-    return mlps::pack_forward(net_flags(flags), params, N, xyz, t, packed, out, saved, stream);
+    return mlps::pack_forward(net_flags(flags), params, N, xyz, t, packed, out, saved, stream,
+                              (flags & DGS_MLP_NO_SAVE) != 0);
 }
 
 extern "C" int dgs_deform_backward(int flags, int N, const float *packed, const float *saved, const float *dout,
@@ -500,4 +595,49 @@ extern "C" int dgs_deform_backward(int flags, int N, const float *packed, const 
     }
     return exact_fp32(flags) ? mlp::backward(net_flags(flags), N, packed, saved, dout, scratch, grads, stream)
                              : mlps::backward(net_flags(flags), N, packed, saved, dout, scratch, grads, stream);
+}
+
+extern "C" int dgs_deform_active_supported(int flags, int N) {
+    return !exact_fp32(flags) && N > 0 && mlps::active_supported(net_flags(flags), N);
+}
+
+extern "C" size_t dgs_deform_active_floats(int flags, int N) { return mlps::active_floats(net_flags(flags), N < 0 ? 0 : N); }
+
+extern "C" int dgs_deform_active_count(int flags, int N, const float *dout, float *active, unsigned *count_host,
+                                       void *stream_) {
+    if (N <= 0 || !dout || !active) {
+        set_error("dgs_deform_active_count: bad argument");
+        return DGS_ERR_ARGS;
+    }
+    return mlps::active_count(net_flags(flags), N, dout, active, count_host, (hipStream_t)stream_);
+}
+
+extern "C" int dgs_deform_backward_active(int flags, int N, const float *xyz, const float *packed, float *saved,
+                                          const float *dout, float *scratch, float *active, unsigned *count_host,
+                                          float *const *grads, void *stream_) {
+    if (N <= 0 || !xyz || !packed || !saved || !dout || !scratch || !active || !grads) {
+        set_error("dgs_deform_backward_active: bad argument");
+        return DGS_ERR_ARGS;
+    }
+    if (!dgs_deform_active_supported(flags, N)) {
+        set_error("dgs_deform_backward_active: not available for these flags / this size (dgs_deform_active_supported)");
+        return DGS_ERR_ARGS;
+    }
+    return mlps::backward_active(net_flags(flags), N, xyz, packed, saved, dout, scratch, active, count_host, grads,
+                                 (hipStream_t)stream_);
+}
+
+extern "C" int dgs_mapped_word_alloc(unsigned **host, unsigned **dev) {
+    if (!host || !dev) {
+        set_error("dgs_mapped_word_alloc: null argument");
+        return DGS_ERR_ARGS;
+    }
+    DGS_HIP_CHECK(hipHostMalloc((void **)host, sizeof(unsigned), hipHostMallocCoherent | hipHostMallocMapped));
+    **host = 0xffffffffu;
+    DGS_HIP_CHECK(hipHostGetDevicePointer((void **)dev, *host, 0));
+    return DGS_OK;
+}
+
+extern "C" void dgs_mapped_word_free(unsigned *host) {
+    if (host) (void)hipHostFree(host);
 }

@@ -21,6 +21,8 @@ struct BwdArgs {
     int flags;
     uint32_t *queue;      // as FwdArgs
     int nblk;
+    const int *n_dev;     // as FwdArgs
+    int ncu;
 };
 
 // relu' bits of a trunk layer's output tiles of this wave, NT n-tiles (the [layer pair][row / 16][64
@@ -60,14 +62,14 @@ __device__ inline void load_wstats_bwd(const BwdArgs &a, ScaleLDS *sc) {
 
 // dOut -> dz rows Z_G (heads' dW) and the split G image, scaled by its max |dOut| per column tile
 template <int NQB, int NTH>
-__device__ inline void stage_dout(const BwdArgs &a, h16x8 *lds, ScaleLDS *sc, float *stage, int p0, int tid) {
+__device__ inline void stage_dout(const BwdArgs &a, h16x8 *lds, ScaleLDS *sc, float *stage, int npts, int p0, int tid) {
     constexpr int BMB = 16 * NQB;
     const Flags F = make_flags(a.flags);
     if (tid < 32) (&sc->bsync[0][0])[tid] = 0;
     for (int e = tid; e < 32 * BMB; e += NTH) {
         const int c = e / BMB, m = e % BMB;
         const int p = p0 + m;
-        const float v = (p < a.N && c < F.nout) ? a.dout[(size_t)p * F.nout + c] : 0.f;
+        const float v = (p < npts && c < F.nout) ? a.dout[(size_t)p * F.nout + c] : 0.f;
         a.dz[(size_t)(Z_G + c) * a.Ns + p] = v;
         stage[c * BM + m] = v;
     }
@@ -139,7 +141,7 @@ __device__ __forceinline__ void chain_epilogue(const BwdArgs &a, h16x8 *lds, uin
     lds_signal(hwr + hk, lane);
 }
 
-// One block of the dX chain (NQB, p0, slot: as fwd_block). NT: n-tiles per wave. NT = 1: 16 waves, two
+// One block of the dX chain (NQB, npts, p0, slot: as fwd_block). NT: n-tiles per wave. NT = 1: 16 waves, two
 // writers per H k-step and step; NT = 2 (k_bwd8: a frame-uniform t, every training step): 8 waves, wave
 // r writes dZ rows 32r .. 32r + 31 = H k-step r (one writer, 8 readers). Same arithmetic, scales,
 // layouts and outputs either way.
@@ -147,7 +149,7 @@ __device__ __forceinline__ void chain_epilogue(const BwdArgs &a, h16x8 *lds, uin
 // t_emb registers or code (raw t PE has no parameters upstream; uniform t: k_tgrad)
 template <bool TE_ROWS, int NQB, int NT>
 __device__ __forceinline__ void bwd_block(const BwdArgs &a, h16x8 *lds, uint32_t *hwr, uint32_t *hrd, ScaleLDS *sc,
-                                          int p0, int slot) {
+                                          int npts, int p0, int slot) {
     static_assert(NT == 1 || (NT == 2 && !TE_ROWS), "two n-tiles per wave: no t_emb rows");
     constexpr uint32_t HWR = 2 / NT;  // writer waves of an H k-step
     float *lf = reinterpret_cast<float *>(lds);
@@ -167,7 +169,7 @@ __device__ __forceinline__ void bwd_block(const BwdArgs &a, h16x8 *lds, uint32_t
         hwr[tid] = 0;
         hrd[tid] = 0;
     }
-    stage_dout<NQB, NTHR / NT>(a, lds, sc, stage, p0, tid);
+    stage_dout<NQB, NTHR / NT>(a, lds, sc, stage, npts, p0, tid);
     f32x4 c[NT][NQB];
     float ib[NQB];
     // The dZ chain runs without workgroup barriers (see fwd_block's trunk): step 0 (heads^T) and steps
@@ -252,16 +254,23 @@ __device__ __forceinline__ void bwd_kernel(const BwdArgs &a) {
     __shared__ ScaleLDS sc;
     load_wstats_bwd(a, &sc);
     CLK_BEGIN();
-    for (int b = blockIdx.x;;) {  // persistent: as fwd_kernel
+    int npts = a.N, nfull = a.nfull, nblk = a.nblk;
+    if (a.n_dev) {  // as fwd_kernel
+        npts = device_points(a.n_dev, a.N);
+        const Blocks bs = split_blocks(npts, a.ncu);
+        nfull = bs.nfull;
+        nblk = bs.nfull + bs.ntail;
+    }
+    for (int b = blockIdx.x; b < nblk;) {  // persistent: as fwd_kernel
         int nx = 0;
         if (a.queue && threadIdx.x == 0) nx = queue_take(a.queue);
-        if (b < a.nfull) bwd_block<TE_ROWS, NQ, NT>(a, lds, hwr, hrd, &sc, b * BM, b);
-        else bwd_block<TE_ROWS, 1, NT>(a, lds, hwr, hrd, &sc, a.nfull * BM + (b - a.nfull) * 16, b);
+        if (b < nfull) bwd_block<TE_ROWS, NQ, NT>(a, lds, hwr, hrd, &sc, npts, b * BM, b);
+        else bwd_block<TE_ROWS, 1, NT>(a, lds, hwr, hrd, &sc, npts, nfull * BM + (b - nfull) * 16, b);
         if (!a.queue) break;
         if (threadIdx.x == 0) s_next = nx;
         __syncthreads();
         b = s_next;
-        if (b >= a.nblk) break;
+        if (b >= nblk) break;
     }
     if (a.queue) queue_release(a.queue);
     if constexpr (NT == 1) CLK_END(1);  // (diagnostic clock stamps: the 16-wave kernels only)

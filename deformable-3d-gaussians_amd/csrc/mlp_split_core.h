@@ -567,6 +567,29 @@ __device__ __forceinline__ int qof(int m) { return m >> 4; }
 // computes exactly what it computed before (same points, same mask slot): outputs are bitwise
 // unchanged. The index of the next block is fetched at the start of the current one (latency hidden
 // by the block); the last workgroup to finish zeroes the counter pair for the next launch.
+// Block decomposition of the fused forward / dX kernels (one 147 KB workgroup per CU): when the last
+// round of 64-point blocks would occupy at most a quarter of the ncu CUs, those blocks run as four times
+// as many 16-point blocks instead (fwd_block / bwd_block NQB = 1), so the sparse last round ends in
+// roughly a third of a full block's time (the A stream, not the MFMAs, bounds a 16-point block).
+// ncu = 0 keeps 64-point blocks throughout. Mask slots: one per block (<= nb + 3 min(nb, 128)).
+// Host and device: a launch whose point count is only known on the device (n_dev of FwdArgs / BwdArgs,
+// the active set of mlp_active.h) derives its blocks from it there.
+constexpr int TAIL_MAX_LAST = 128;
+struct Blocks {
+    int nfull, ntail;
+};
+__host__ __device__ inline Blocks split_blocks(int N, int ncu) {
+    const int nb = div_up(N, BM);
+    if (ncu <= 0 || nb == 0) return {nb, 0};
+    const int rounds = div_up(nb, ncu), last = nb - ncu * (rounds - 1);
+    if (rounds < 2 || last > TAIL_MAX_LAST || 4 * last > ncu) return {nb, 0};
+    return {nb - last, 4 * last};
+}
+// n_dev launches: the device word's point count, clamped to the launch's N (a wave-uniform value)
+__device__ __forceinline__ int device_points(const int *n_dev, int N) {
+    return min(max(__builtin_amdgcn_readfirstlane(*n_dev), 0), N);
+}
+
 __device__ __forceinline__ int queue_take(uint32_t *q) { return (int)gridDim.x + (int)atomicAdd(q, 1u); }
 __device__ __forceinline__ void queue_release(uint32_t *q) {
     // every workgroup's final take has returned before its increment of q[1]

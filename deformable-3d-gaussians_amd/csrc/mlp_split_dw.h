@@ -31,6 +31,9 @@ namespace mlps {
 //   Output: ROW jobs' tiles are [dZ row][X row] (the slab's own layout, stored as before); COL jobs'
 // are [X row][dZ row] and go through a per-wave LDS transpose so the slab stores stay coalesced.
 // Same job plan, slab layout and k_dw_reduce (mlp_dw_reduce.h) as the fp32 k_dw (mlp_dw_fp32.h).
+//   Ns is the row stride of both operands; ext <= Ns (a multiple of BM) is the extent the chunks cover: the
+// whole allocation, or the active set's padded point count (n_dev, mlp_active.h), beyond which the rows
+// hold other launches' values that no chunk reads. ext = 0: every slab is written as zeros.
 // ------------------------------------------------------------------------------------------------
 constexpr int DW_THREADS = 512;
 constexpr int S_UNITS = NSPLIT * 2 * 8 * 64;  // 16-B units per chunk buffer
@@ -97,7 +100,7 @@ __device__ __forceinline__ float max8(float v) {
 }
 
 template <bool COL, int NS>
-__device__ __forceinline__ void dws_run(const WJob &J, size_t Ns, const float *__restrict__ dz,
+__device__ __forceinline__ void dws_run(const WJob &J, size_t Ns, size_t ext, const float *__restrict__ dz,
                                         const float *__restrict__ saved, float *__restrict__ slabs, h16x8 *lds) {
     constexpr int SROWS = 32 * NS;                   // shared rows staged per chunk
     constexpr int NSF = (SROWS * 8 + 511) / 512;     // staged float4 per thread per chunk
@@ -105,7 +108,7 @@ __device__ __forceinline__ void dws_run(const WJob &J, size_t Ns, const float *_
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int h = lane >> 5, i = lane & 31;
-    const int nch = (int)(Ns / 32);
+    const int nch = (int)(ext / 32);
     const int per = div_up(nch, J.nsplit);
     const int c0 = split * per;
     const int c1 = min(nch, c0 + per);
@@ -293,9 +296,11 @@ __device__ __forceinline__ void dws_run(const WJob &J, size_t Ns, const float *_
     }
 }
 
-__global__ __launch_bounds__(DW_THREADS) void k_dws(WJobs JT, size_t Ns, const float *__restrict__ dz,
-                                                    const float *__restrict__ saved, float *__restrict__ slabs) {
+__global__ __launch_bounds__(DW_THREADS) void k_dws(WJobs JT, size_t Ns, int N, const int *__restrict__ n_dev,
+                                                    const float *__restrict__ dz, const float *__restrict__ saved,
+                                                    float *__restrict__ slabs) {
     extern __shared__ h16x8 dws_lds[];
+    const size_t ext = n_dev ? (size_t)div_up(device_points(n_dev, N), BM) * BM : Ns;
     WJob J = JT.j[0];
 #pragma unroll
     for (int q = 1; q < MAXJ; q++)
@@ -305,15 +310,15 @@ __global__ __launch_bounds__(DW_THREADS) void k_dws(WJobs JT, size_t Ns, const f
     CLK_BEGIN();
     if (J.krows == 256) {
         if (J.nrows == 256)
-            dws_run<true, 8>(J, Ns, dz, saved, slabs, dws_lds);
+            dws_run<true, 8>(J, Ns, ext, dz, saved, slabs, dws_lds);
         else
-            dws_run<true, 1>(J, Ns, dz, saved, slabs, dws_lds);
+            dws_run<true, 1>(J, Ns, ext, dz, saved, slabs, dws_lds);
     } else if (J.krows > 64) {
-        dws_run<false, 3>(J, Ns, dz, saved, slabs, dws_lds);
+        dws_run<false, 3>(J, Ns, ext, dz, saved, slabs, dws_lds);
     } else if (J.krows > 32) {
-        dws_run<false, 2>(J, Ns, dz, saved, slabs, dws_lds);
+        dws_run<false, 2>(J, Ns, ext, dz, saved, slabs, dws_lds);
     } else {
-        dws_run<false, 1>(J, Ns, dz, saved, slabs, dws_lds);
+        dws_run<false, 1>(J, Ns, ext, dz, saved, slabs, dws_lds);
     }
     CLK_END(2);
 }

@@ -27,6 +27,11 @@ struct FwdArgs {
     int flags;
     uint32_t *queue;  // block queue (persistent launch, BlockQueue) or nullptr: one launch block per block
     int nblk;         // blocks (64-point + 16-point)
+    // the point count in device memory (the active set, mlp_active.h) or nullptr: the kernel clamps it
+    // to N and derives nfull / nblk from it (split_blocks over ncu CUs); N, nfull and nblk above then
+    // only size the grid and the buffers, and Ns stays the row stride of `saved`
+    const int *n_dev;
+    int ncu;
 };
 
 // The reference feeds every Gaussian the same frame time (train_baseline.py:107-110), so the
@@ -98,7 +103,7 @@ __global__ __launch_bounds__(256) void k_timenet(FwdArgs a) {
 
 // One block of NQB 16-point column tiles (NQB = 4: the 64-point blocks; NQB = 1: the 16-point tail
 // blocks that spread the last, sparse round of blocks over the idle CUs). p0: first point; slot: the
-// block's relu'-mask slot.
+// block's relu'-mask slot; npts: the launch's point count (a.N, or the device's: FwdArgs::n_dev).
 // NT: n-tiles per wave. NT = 1: 16 waves (4 per SIMD), wave r owns rows 16r .. 16r + 15 of every trunk
 // layer, so an H k-step has two writers (hand-off target 2 L per layer) and 16 readers. NT = 2: the
 // training forward (saved activations, frame-uniform t folded) as 8 waves (k_fwd8, 512 threads, 2 per
@@ -106,8 +111,8 @@ __global__ __launch_bounds__(256) void k_timenet(FwdArgs a) {
 // readers. Same LDS image, saved-activation / relu'-mask layouts, scales and arithmetic either way.
 template <bool SAVE, int NQB, bool FOLD, int NT>
 __device__ __forceinline__ void fwd_block(const FwdArgs &a, h16x8 *lds, uint32_t *hwr, uint32_t *hrd, const float4 *sb,
-                                          uint32_t *s_mpend, ScaleLDS *sc, int p0, int slot) {
-    static_assert(NT == 1 || (NT == 2 && SAVE && FOLD), "two n-tiles per wave: the training forward only");
+                                          uint32_t *s_mpend, ScaleLDS *sc, int npts, int p0, int slot) {
+    static_assert(NT == 1 || (NT == 2 && FOLD), "two n-tiles per wave: the training forward only");
     constexpr int NW = NWAVE / NT, NTH = 64 * NW;  // waves, threads
     constexpr uint32_t HWR = 2 / NT;               // writer waves of an H k-step
     constexpr int BMB = 16 * NQB;  // points of this block (the LDS images keep the BM-point stride)
@@ -121,7 +126,7 @@ __device__ __forceinline__ void fwd_block(const FwdArgs &a, h16x8 *lds, uint32_t
     const int r = __builtin_amdgcn_readfirstlane(tid >> 6);  // this wave: n-tiles NT r .. (provably uniform)
     const int hk = (NT * r) >> 1;                            // the H k-step its rows are part of
     const int kq = lane >> 4, col = lane & 15;
-    const int pend = min(a.N, p0 + BMB);  // real points of the block: [p0, pend)
+    const int pend = min(npts, p0 + BMB);  // real points of the block: [p0, pend)
     const Flags F = make_flags(a.flags);
     const size_t Ns = a.Ns;
     const __amdgpu_buffer_rsrc_t mrsrc = __builtin_amdgcn_make_buffer_rsrc(
@@ -147,7 +152,7 @@ __device__ __forceinline__ void fwd_block(const FwdArgs &a, h16x8 *lds, uint32_t
     if (!FOLD && F.blender && a.tc && !uniform_t) {
         const float t0 = a.tc[TC_T];
         const int p = p0 + lane;
-        const float tv = (lane < BMB && p < a.N) ? a.t[p] : t0;
+        const float tv = (lane < BMB && p < npts) ? a.t[p] : t0;
         uniform_t = __ballot(tv != t0) == 0;
     }
     // t_emb folded into the linear.0 / linear.5 biases (FOLD = DGS_MLP_UNIFORM_T; the host always
@@ -422,7 +427,7 @@ __device__ __forceinline__ void fwd_block(const FwdArgs &a, h16x8 *lds, uint32_t
         const int p = p0 + 16 * hq + col;
 #pragma unroll
         for (int i = 0; i < 4; i++)
-            if (p < pend && 4 * kq + i < F.nout) a.out[(size_t)p * F.nout + 4 * kq + i] = c1[0][0][i];
+            if (a.out && p < pend && 4 * kq + i < F.nout) a.out[(size_t)p * F.nout + 4 * kq + i] = c1[0][0][i];
     }
     if constexpr (NT == 1) {
         DGS_STAMP(21);
@@ -471,16 +476,23 @@ __device__ __forceinline__ void fwd_kernel(const FwdArgs &a) {
     // the first block's staging barriers publish the bias table
     load_bias_table<FOLD>(a, s_bias, &sc, NTHR / NT);
     CLK_BEGIN();
-    for (int b = blockIdx.x;;) {  // persistent: block after block from the queue (mlp_split_core.h)
+    int npts = a.N, nfull = a.nfull, nblk = a.nblk;
+    if (a.n_dev) {  // the launch was sized for a.N points; the device's count says how many there are
+        npts = device_points(a.n_dev, a.N);
+        const Blocks bs = split_blocks(npts, a.ncu);
+        nfull = bs.nfull;
+        nblk = bs.nfull + bs.ntail;
+    }
+    for (int b = blockIdx.x; b < nblk;) {  // persistent: block after block from the queue (mlp_split_core.h)
         int nx = 0;
         if (a.queue && threadIdx.x == 0) nx = queue_take(a.queue);
-        if (b < a.nfull) fwd_block<SAVE, NQ, FOLD, NT>(a, lds, hwr, hrd, s_bias, s_mpend, &sc, b * BM, b);
-        else fwd_block<SAVE, 1, FOLD, NT>(a, lds, hwr, hrd, s_bias, s_mpend, &sc, a.nfull * BM + (b - a.nfull) * 16, b);
+        if (b < nfull) fwd_block<SAVE, NQ, FOLD, NT>(a, lds, hwr, hrd, s_bias, s_mpend, &sc, npts, b * BM, b);
+        else fwd_block<SAVE, 1, FOLD, NT>(a, lds, hwr, hrd, s_bias, s_mpend, &sc, npts, nfull * BM + (b - nfull) * 16, b);
         if (!a.queue) break;
         if (threadIdx.x == 0) s_next = nx;
         __syncthreads();  // also: the next block's staging overwrites LDS this one's heads read
         b = s_next;
-        if (b >= a.nblk) break;
+        if (b >= nblk) break;
     }
     if (a.queue) queue_release(a.queue);
     if constexpr (NT == 1) CLK_END(0);  // (diagnostic clock stamps: the 16-wave kernels only)
@@ -493,6 +505,9 @@ __global__ __launch_bounds__(NTHR) void k_fwd(FwdArgs a) {
 
 // the training forward (saved activations, frame-uniform t folded): 8 waves of two n-tiles
 __global__ __launch_bounds__(NTHR8) void k_fwd8(FwdArgs a) { fwd_kernel<true, true, 2>(a); }
+// the same block with the saved-row and relu'-mask stores compiled out: `out` is bitwise k_fwd8's (the
+// step's first forward when the saved activations are recomputed on the active set, mlp_active.h)
+__global__ __launch_bounds__(NTHR8) void k_fwd8_nosave(FwdArgs a) { fwd_kernel<false, true, 2>(a); }
 
 }  // namespace mlps
 }  // namespace dgs

@@ -22,6 +22,23 @@ __global__ void k_fill_scalar(int n, const float *__restrict__ v, float *__restr
 
 constexpr int M_REST = 15;
 
+// the step's network backward recomputes on the active set (mlp_active.h); the same answer in both phases
+bool active_set(const dgs_train_step_args *a, int flags) {
+    return a->mlp_active && a->mlp_active_mode == 1 && dgs_deform_active_supported(flags, a->P);
+}
+
+// the network backward: over the active set, or over every row (counting the active ones when asked to)
+int network_backward(const dgs_train_step_args *a, int flags, hipStream_t stream) {
+    if (active_set(a, flags))
+        return dgs_deform_backward_active(flags, a->P, a->xyz, a->mlp_packed, a->mlp_saved, a->mlp_dout, a->mlp_scratch,
+                                          a->mlp_active, a->mlp_active_count, a->mlp_grads, stream);
+    if (a->mlp_active && a->P > 0 && !(flags & DGS_MLP_EXACT_FP32))
+        if (int rc = dgs_deform_active_count(flags, a->P, a->mlp_dout, a->mlp_active, a->mlp_active_count, stream))
+            return rc;
+    return dgs_deform_backward(flags, a->P, a->mlp_packed, a->mlp_saved, a->mlp_dout, a->mlp_scratch, a->mlp_grads,
+                               stream);
+}
+
 }  // namespace
 }  // namespace dgs
 
@@ -49,9 +66,7 @@ extern "C" int dgs_train_step(const dgs_train_step_args *a, int *overflowed, int
     }
     const int flags = a->mlp_flags | DGS_MLP_UNIFORM_T;
     if (phase == 2)  // the network backward of the preceding phase-1 call
-        return warm ? dgs_deform_backward(flags, P, a->mlp_packed, a->mlp_saved, a->mlp_dout, a->mlp_scratch,
-                                          a->mlp_grads, stream)
-                    : DGS_OK;
+        return warm ? network_backward(a, flags, stream) : DGS_OK;
     long long over0 = dgs_raster_deferred_overflows();
     // ---- deform.step(xyz.detach(), t) (scene/deform_model.py:323-324) with one frame time ----
     if (warm) {
@@ -67,8 +82,9 @@ extern "C" int dgs_train_step(const dgs_train_step_args *a, int *overflowed, int
             t = a->t_full;
         }
         // pack + forward (k_pack, k_timenet, the forward: mlp_split.hip pack_forward)
-        if (int rc = dgs_deform_pack_forward(flags, a->mlp_params, P, a->xyz, t, a->mlp_packed, a->mlp_out,
-                                             a->mlp_saved, stream))
+        // (the active-set step: nothing saved, the backward recomputes what it needs)
+        if (int rc = dgs_deform_pack_forward(flags | (active_set(a, flags) ? DGS_MLP_NO_SAVE : 0), a->mlp_params, P,
+                                             a->xyz, t, a->mlp_packed, a->mlp_out, a->mlp_saved, stream))
             return rc;
     }
     // ---- render(): input glue, then the split-SH rasterizer (gaussian_renderer/__init__.py:32-133) ----
@@ -115,8 +131,7 @@ extern "C" int dgs_train_step(const dgs_train_step_args *a, int *overflowed, int
                                               a->g_scaling, a->g_rotation, a->g_opacity, warm ? a->mlp_dout : nullptr,
                                               warm ? nout : 10, stream);
     }
-    if (!rc && warm && phase == 3) rc = dgs_deform_backward(flags, P, a->mlp_packed, a->mlp_saved, a->mlp_dout, a->mlp_scratch,
-                                              a->mlp_grads, stream);
+    if (!rc && warm && phase == 3) rc = network_backward(a, flags, stream);
     // the whole step (phase 1: up to the Gaussian gradients) is queued: now the deferred pair count may
     // be resolved (a host wait at most)
     if (num_rendered) *num_rendered = nr >= 0 ? nr : dgs_raster_ctx_num_rendered(ctx);

@@ -108,6 +108,12 @@ _SIGS = {
     "dgs_deform_pack_forward": ([I, P, I, P, P, P, P, P, P], I),
     "dgs_deform_backward": ([I, I, P, P, P, P, P, P], I),
     "dgs_deform_outputs": ([I], I),
+    "dgs_deform_active_supported": ([I, I], I),
+    "dgs_deform_active_floats": ([I, I], SZ),
+    "dgs_deform_active_count": ([I, I, P, P, P, P], I),
+    "dgs_deform_backward_active": ([I, I, P, P, P, P, P, P, P, P, P], I),
+    "dgs_mapped_word_alloc": ([P, P], I),
+    "dgs_mapped_word_free": ([P], None),
     "dgs_knn_dist2": ([I, P, P, P], I),
     "dgs_l1_ssim_scratch_floats": ([I, I, I], SZ),
     "dgs_l1_ssim_window": ([P], None),

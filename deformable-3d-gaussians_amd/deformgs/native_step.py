@@ -16,6 +16,16 @@ all-reduce of the Gaussian gradients (a flat buffer the parameters' .grad tensor
 concatenation, no copy back) is started and overlaps phase 2, the network backward; then the network
 gradients' all-reduce. The autograd path's hooks (dist.OverlappedGradAllReduce) do the same
 overlap with a concatenation per step.
+
+The network backward over the active set (csrc/mlp_active.h): DGS_MLP_ACTIVE_SET=0 keeps
+the full backward, 1 forces the recompute path wherever the kernels allow it, auto (the default)
+chooses per step from the running fraction f of Gaussians with a nonzero output gradient. The device
+stores each step's count into a mapped host word that is read at the start of the next call and never
+waited on; a model's first step (and every step until a count has arrived) takes the full backward.
+Either path gives the same gradients up to summation order, so a wrong guess only costs time. With the
+deterministic rasterizer backward (renderer.set_deterministic) auto keeps the full backward: which
+count has arrived by a given step is a matter of timing, and a bitwise-reproducible loop must not depend
+on it.
 """
 import ctypes
 import math
@@ -44,7 +54,53 @@ class TrainStepArgs(ctypes.Structure):
         ("d_rotations", P_),
         ("g_xyz", P_), ("g_dc", P_), ("g_rest", P_), ("g_scaling", P_), ("g_rotation", P_), ("g_opacity", P_),
         ("deferred_count", I_), ("phase", I_),
+        ("mlp_active", P_), ("mlp_active_count", P_), ("mlp_active_mode", I_),
     ]
+
+
+# auto takes the recompute path while the running active fraction is below this: the kernel times
+# measured at f = 0.50 and f = 0.94 break even at f = 0.72
+ACTIVE_BREAK_EVEN = 0.7
+
+
+def active_set_mode():
+    """DGS_MLP_ACTIVE_SET: '0', '1' or 'auto' (default; anything else reads as auto)."""
+    v = os.environ.get("DGS_MLP_ACTIVE_SET", "auto").strip().lower()
+    return v if v in ("0", "1") else "auto"
+
+
+class _MappedWord:
+    """A pinned host word the device stores to (dgs_mapped_word_alloc); 0xffffffff until it has. Words
+    are never freed while the process runs: a queued kernel may still store to the word of a NativeStep
+    that is gone, and freeing it safely would take a device wait. A dropped word goes back to a free list
+    and is handed out again; a late store into it gives its next owner one wrong count, which only costs
+    time."""
+    _free = []
+
+    def __init__(self, lib):
+        if _MappedWord._free:
+            self.host, self.dev = _MappedWord._free.pop()
+        else:
+            host, dev = P_(), P_()
+            _lib.check(lib.dgs_mapped_word_alloc(ctypes.byref(host), ctypes.byref(dev)), "mapped_word_alloc")
+            self.host, self.dev = host.value, dev.value
+        self._view = ctypes.c_uint32.from_address(self.host)
+        self._view.value = 0xFFFFFFFF
+
+    def take(self):
+        """The value the device has stored since the last take(), or None. (A store that lands between the
+        read and the reset is lost: the next step's takes its place.)"""
+        v = self._view.value
+        if v == 0xFFFFFFFF:
+            return None
+        self._view.value = 0xFFFFFFFF
+        return v
+
+    def __del__(self):
+        try:
+            _MappedWord._free.append((self.host, self.dev))
+        except Exception:
+            pass
 
 
 def enabled():
@@ -78,6 +134,11 @@ class NativeStep:
         self.gs, self.deform = gaussians, deform
         self.key = None
         self.lib = _lib.load()
+        self.active_fraction = None   # running f of this model's Gaussian set (None: no count yet)
+        self.active_last = None       # the fraction of the latest count that has arrived
+        self.active_used = False      # whether the last step took the recompute path
+        self.steps = self.active_steps = 0   # warm steps issued, and those of them on the recompute path
+        self._count_word = None
 
     def _params(self):
         g = self.gs
@@ -118,7 +179,17 @@ class NativeStep:
             "mlp_saved": e(lib.dgs_deform_saved_floats(flags | 16, N)),
             "mlp_scratch": e(lib.dgs_deform_scratch_floats(flags | 16, N)),
             "mlp_out": e(N, nout), "mlp_dout": e(N, nout), "t_full": e(max(N, 1)),
+            "mlp_active": e(max(1, lib.dgs_deform_active_floats(flags | 16, N))),
         }
+        # a new Gaussian set: its first step takes the full backward again
+        self._active_ok = bool(lib.dgs_deform_active_supported(flags | 16, N))
+        # one word per NativeStep, kept across rebuilds (a count of the previous set that is still in
+        # flight is taken once against the new N: harmless, f is clamped to 1)
+        if self._active_ok and self._count_word is None:
+            self._count_word = _MappedWord(lib)
+        if self._count_word is not None:
+            self._count_word.take()
+        self.active_fraction = self.active_last = None
         # persistent parameter gradients (handed to the parameters as .grad; overwritten every step),
         # views of one flat buffer per group (the data-parallel all-reduce runs on it in place)
         self.gflat, self.ggrads = _flat_views(gp)
@@ -138,7 +209,32 @@ class NativeStep:
                   "d_means2D", "d_means2D_densify", "d_opacities", "d_scales", "d_rotations"):
             setattr(a, k, b[k].data_ptr())
         a.g_xyz, a.g_dc, a.g_rest, a.g_scaling, a.g_rotation, a.g_opacity = (g.data_ptr() for g in self.ggrads)
+        a.mlp_active = b["mlp_active"].data_ptr() if self._active_ok else None
+        a.mlp_active_count = self._count_word.dev if self._active_ok else None
+        a.mlp_active_mode = 0
         self.key = key
+
+    def _choose_active(self):
+        """1 when this step's network backward runs over the active set. Takes a count the device has
+        stored since the last call (one step late or more; never waited on) into the running fraction;
+        each count enters once. Where the count cannot bear on a decision (DGS_MLP_ACTIVE_SET=0, the
+        deterministic mode under auto) the step does not count either."""
+        a = self.args
+        a.mlp_active = None
+        if not self._active_ok:
+            return 0
+        m = self._count_word.take()
+        if m is not None:
+            f = min(1.0, m / max(1, a.P))
+            self.active_last = f
+            self.active_fraction = f if self.active_fraction is None else 0.75 * self.active_fraction + 0.25 * f
+        mode = active_set_mode()
+        if mode == "0" or (mode == "auto" and self.lib.dgs_raster_get_deterministic()):
+            return 0
+        a.mlp_active = self.buf["mlp_active"].data_ptr()
+        if mode == "1":
+            return 1
+        return 1 if self.active_fraction is not None and self.active_fraction < ACTIVE_BREAK_EVEN else 0
 
     def __call__(self, cam, gt_image, background, warm=True, ast_noise=0.0, lambda_dssim=0.2, deferred_count=False,
                  phase=0):
@@ -173,6 +269,10 @@ class NativeStep:
         a.image, a.loss3 = image.data_ptr(), loss3.data_ptr()
         a.deferred_count = 1 if deferred_count else 0
         a.phase = phase
+        a.mlp_active_mode = self._choose_active() if warm else 0
+        self.active_used = bool(a.mlp_active_mode)
+        self.steps += int(warm)
+        self.active_steps += int(self.active_used)
         self._warm = warm
         over, nr = I_(0), I_(0)
         _lib.check(lib.dgs_train_step(ctypes.byref(a), ctypes.byref(over), ctypes.byref(nr), _lib.stream_ptr(dev)),

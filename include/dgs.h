@@ -204,12 +204,16 @@ enum {
     DGS_MLP_6DOF = 2,      /* heads branch_w(3), branch_v(3) instead of gaussian_warp(3) */
     DGS_MLP_NO_ROTSCALE = 4, /* DeformNetwork fork variant: rotation/scaling heads unused */
     DGS_MLP_EXACT_FP32 = 8, /* fp32-input MFMA path instead of the split-f16 path */
-    DGS_MLP_UNIFORM_T = 16  /* caller guarantees t[i] == t[0] for every point (one frame time, as
+    DGS_MLP_UNIFORM_T = 16, /* caller guarantees t[i] == t[0] for every point (one frame time, as
                                train_baseline.py:107-110 feeds it): the timenet runs once per launch,
                                t_emb is folded into the linear.0 / linear.5 biases (outputs equal the
                                per-point path to fp32 rounding), and the timenet / t_emb-column
                                gradients are formed from the layer-0/5 bias gradients instead of
                                per-point sums (split path, blender only; ignored otherwise) */
+    DGS_MLP_NO_SAVE = 32   /* dgs_deform_forward / _pack_forward only, with DGS_MLP_UNIFORM_T and a
+                               saved buffer: the same forward kernel with its saved-activation and
+                               relu'-mask stores compiled out (out bitwise equal); only the timenet's
+                               constants are left in `saved`, for dgs_deform_backward_active */
 };
 
 /* Parameter table: device pointers in state_dict order of DeformNetworkBaseline
@@ -234,6 +238,27 @@ int dgs_deform_pack_forward(int flags, const float *const *params, int N, const 
 int dgs_deform_backward(int flags, int N, const float *packed, const float *saved, const float *dout,
                         float *scratch, float *const *grads, void *stream);
 int dgs_deform_outputs(int flags);
+/* The backward over the active set only: the rows of dout with any nonzero element (+-0 are zero). A
+ * row of zeros adds exactly +0 to every parameter gradient, so the gradients equal dgs_deform_backward's
+ * up to summation order (and the last bits of recomputed activations: a 16-point tile shares one split
+ * scale). Follows a forward with DGS_MLP_NO_SAVE on the same packed / saved buffers (xyz: that forward's):
+ * the active rows' xyz and dout are compacted on the device in ascending index order, the saving forward
+ * reruns on those M points, then the dX chain and the dW GEMM run on M points. M stays on the device
+ * (first word of `active`, an int); count_host, when given, is the device address of a mapped host word
+ * (dgs_mapped_word_alloc) that receives M as well. No host wait. Bitwise deterministic.
+ * active: dgs_deform_active_floats(flags, N) floats. dgs_deform_active_supported: 1 when the flags and N
+ * allow it (split path, DGS_MLP_UNIFORM_T on a blender network, the split dW within its offsets).
+ * dgs_deform_active_count only counts: M to `active` and count_host (steps that keep the full backward). */
+int dgs_deform_active_supported(int flags, int N);
+size_t dgs_deform_active_floats(int flags, int N);
+int dgs_deform_active_count(int flags, int N, const float *dout, float *active, unsigned *count_host, void *stream);
+int dgs_deform_backward_active(int flags, int N, const float *xyz, const float *packed, float *saved,
+                               const float *dout, float *scratch, float *active, unsigned *count_host,
+                               float *const *grads, void *stream);
+/* One host word the device can store to (pinned, coherent, mapped), initialised to 0xffffffff; *dev is
+ * its device address. Read it through *host whenever convenient: no wait is implied. */
+int dgs_mapped_word_alloc(unsigned **host, unsigned **dev);
+void dgs_mapped_word_free(unsigned *host);
 
 /* ---- fused photometric loss (utils/loss_utils.py:18-73, train_baseline.py:126-127) ----
  * img, gt: (C,H,W). out3 (device) = [loss, mean L1, mean SSIM] with
@@ -375,6 +400,14 @@ typedef struct dgs_train_step_args {
     float *g_xyz, *g_dc, *g_rest, *g_scaling, *g_rotation, *g_opacity;  /* parameter gradients */
     int deferred_count;
     int phase;                           /* 0 (= 3), 1, 2, 3: see above */
+    /* the network backward over the active set (dgs_deform_backward_active). mlp_active: NULL, or
+     * dgs_deform_active_floats floats. mlp_active_mode: 1 = the first forward saves nothing and the
+     * backward recomputes on the active set (ignored where dgs_deform_active_supported is 0); 0 = the full
+     * backward, and with mlp_active given the active rows are still counted. mlp_active_count: NULL or a
+     * mapped word's device address that receives the count. The same values in the phase 1 and 2 calls. */
+    float *mlp_active;
+    unsigned *mlp_active_count;
+    int mlp_active_mode;
 } dgs_train_step_args;
 int dgs_train_step(const dgs_train_step_args *a, int *overflowed, int *num_rendered, void *stream);
 
