@@ -5,7 +5,8 @@ reader readNerfiesInfo (NeRF-DS, HyperNeRF vrig / interp / misc).
 Mirrors (file:line in the reference):
   scene/dataset_readers.py:223-266  readCamerasFromTransforms: R / T from transform_matrix, fid = frame["time"],
                                     FovY = camera_angle_x and FovX from it (the names are swapped there, and
-                                    the swap is kept, as deformgs/render_cli.read_transforms does)
+                                    the swap is kept); transforms_frames parses the file for this reader and
+                                    for the render script's (deformgs/render_cli.read_transforms)
   scene/dataset_readers.py:269-306  readNerfSyntheticInfo: test merged into train unless eval; getNerfppNorm;
                                     points3d.ply or 100 000 random points in [-1.3, 1.3]^3
   scene/dataset_readers.py:398-473  readNerfiesCameras: scene.json / metadata.json / dataset.json, the split rule
@@ -50,6 +51,7 @@ import numpy as np
 import torch
 
 from .cameras import Camera, blender_c2w_to_RT, focal2fov, fov2focal, getWorld2View2
+from .ingest import image_header, ingest_images
 from .sh import C0
 
 CameraInfo = namedtuple("CameraInfo", "uid R T FovY FovX image_path image_name width height fid")
@@ -61,13 +63,18 @@ _PLY_TYPES = {"float": "<f4", "float32": "<f4", "double": "<f8", "float64": "<f8
               "int": "<i4", "int32": "<i4", "uint": "<u4", "uint32": "<u4"}
 
 
+def _header(path):
+    """ingest.image_header of a file: (format, width, height, PNG colour type) from its first 26 bytes."""
+    with open(path, "rb") as f:
+        return image_header(f.read(26))
+
+
 def png_size(path):
     """(width, height) from the IHDR of a PNG file (no decode)."""
-    with open(path, "rb") as f:
-        head = f.read(24)
-    if len(head) < 24 or head[:8] != b"\x89PNG\r\n\x1a\n" or head[12:16] != b"IHDR":
+    fmt, width, height, _ = _header(path)
+    if fmt != "png" or width is None:
         raise ValueError(f"{path}: not a PNG file")
-    return int.from_bytes(head[16:20], "big"), int.from_bytes(head[20:24], "big")
+    return width, height
 
 
 def jpeg_size(path):
@@ -78,28 +85,39 @@ def jpeg_size(path):
 
 def image_size(path):
     """(width, height) of a PNG or JPEG file, told apart by the signature; header only."""
-    with open(path, "rb") as f:
-        head = f.read(8)
-    if head[:2] == b"\xff\xd8":
-        return jpeg_size(path)
-    return png_size(path)
+    return jpeg_size(path) if _header(path)[0] == "jpeg" else png_size(path)
 
 
-def read_cameras_from_transforms(path, transformsfile, extension=".png"):
-    """dataset_readers.py:223-266 without the image load (the images are ingested per set, in one batch)."""
+def transforms_frames(path, transformsfile, extension=".png"):
+    """A D-NeRF transforms_*.json under `path` -> per frame (R, T, camera_angle_x, time or None, image path or
+    None): the one parser of that file. Sizes, fields of view and what a missing time or file means are the
+    callers'."""
     with open(os.path.join(path, transformsfile)) as f:
         contents = json.load(f)
     fovx = contents["camera_angle_x"]
+    return [blender_c2w_to_RT(np.array(frame["transform_matrix"])) +
+            (fovx, frame.get("time"), os.path.join(path, frame["file_path"] + extension) if "file_path" in frame else None)
+            for frame in contents["frames"]]
+
+
+def transforms_camera(idx, R, T, fovx, fid, image_path, width, height):
+    """The CameraInfo of one transforms frame at a frame size: dataset_readers.py:256-262."""
+    fovy = focal2fov(fov2focal(fovx, width), height)
+    # :257-259 swaps the names: FovY = fovx, FovX = fovy
+    return CameraInfo(uid=idx, R=R, T=T, FovY=fovx, FovX=fovy, image_path=image_path,
+                      image_name=os.path.splitext(os.path.basename(image_path))[0] if image_path else None,
+                      width=width, height=height, fid=fid)
+
+
+def read_cameras_from_transforms(path, transformsfile, extension=".png"):
+    """dataset_readers.py:223-266 without the image load (the images are ingested per set, in one batch). The size
+    is the PNG header's; a frame without file_path or time is a KeyError."""
     infos = []
-    for idx, frame in enumerate(contents["frames"]):
-        image_path = os.path.join(path, frame["file_path"] + extension)
-        R, T = blender_c2w_to_RT(np.array(frame["transform_matrix"]))
-        width, height = png_size(image_path)
-        fovy = focal2fov(fov2focal(fovx, width), height)
-        # :257-259 swaps the names: FovY = fovx, FovX = fovy
-        infos.append(CameraInfo(uid=idx, R=R, T=T, FovY=fovx, FovX=fovy, image_path=image_path,
-                                image_name=os.path.splitext(os.path.basename(image_path))[0], width=width,
-                                height=height, fid=frame["time"]))
+    for idx, (R, T, fovx, time, image_path) in enumerate(transforms_frames(path, transformsfile, extension)):
+        for key, value in (("file_path", image_path), ("time", time)):
+            if value is None:
+                raise KeyError(key)
+        infos.append(transforms_camera(idx, R, T, fovx, time, image_path, *png_size(image_path)))
     return infos
 
 
@@ -176,31 +194,40 @@ def random_point_cloud(num_pts, seed=0):
     return xyz, shs * C0 + 0.5
 
 
+def start_point_cloud(source_ply, make_points, model_path, normals_dtype=np.float64):
+    """The start-up cloud of every reader -> (BasicPointCloud, ply_path). SOURCE's own .ply if present; otherwise
+    make_points() -> (xyz, rgb on the 0..255 scale), written to MODEL/input.ply when model_path is given (never
+    under SOURCE) and read back from there, so the colours carry the file's 8-bit truncation as upstream. Without
+    a model_path the same cloud is built in memory and ply_path is None; its zero normals have the dtype the
+    reader asks for (the Colmap reader's are float32, the other two's float64)."""
+    if os.path.exists(source_ply):
+        return fetch_ply(source_ply), source_ply
+    xyz, rgb = make_points()
+    if model_path:
+        os.makedirs(model_path, exist_ok=True)
+        ply_path = os.path.join(model_path, "input.ply")
+        store_ply(ply_path, xyz, rgb)
+        return fetch_ply(ply_path), ply_path
+    return BasicPointCloud(points=xyz.astype(np.float32), colors=rgb.astype(np.uint8) / 255.0,
+                           normals=np.zeros((xyz.shape[0], 3), normals_dtype)), None
+
+
 def read_nerf_synthetic(path, white_background, eval, extension=".png", init_points=100_000, model_path=None, seed=0):
     """dataset_readers.py:269-306. white_background is applied when the images are ingested (Scene); it is
     kept in the signature of the reference. The point cloud is SOURCE/points3d.ply if present; otherwise
-    `init_points` seeded random points, written to MODEL/input.ply when model_path is given (never under
-    SOURCE) and read back from there, so the colours carry the file's 8-bit rounding as upstream."""
+    `init_points` seeded random points (start_point_cloud)."""
     train = read_cameras_from_transforms(path, "transforms_train.json", extension)
     test = read_cameras_from_transforms(path, "transforms_test.json", extension)
     if not eval:
         train.extend(test)
         test = []
     norm = nerfpp_norm(train)
-    ply_path = os.path.join(path, "points3d.ply")
-    if os.path.exists(ply_path):
-        pcd = fetch_ply(ply_path)
-    else:
+
+    def points():
         xyz, rgb = random_point_cloud(init_points, seed)
-        ply_path = None
-        if model_path:
-            os.makedirs(model_path, exist_ok=True)
-            ply_path = os.path.join(model_path, "input.ply")
-            store_ply(ply_path, xyz, rgb * 255)
-            pcd = fetch_ply(ply_path)
-        else:
-            pcd = BasicPointCloud(points=xyz.astype(np.float32), colors=(rgb * 255).astype(np.uint8) / 255.0,
-                                  normals=np.zeros((init_points, 3)))
+        return xyz, rgb * 255
+
+    pcd, ply_path = start_point_cloud(os.path.join(path, "points3d.ply"), points, model_path)
     return SceneInfo(point_cloud=pcd, train_cameras=train, test_cameras=test, nerf_normalization=norm, ply_path=ply_path)
 
 
@@ -279,30 +306,20 @@ def read_nerfies_cameras(path, nerfies_kind=None):
 
 def read_nerfies(path, eval, model_path=None, nerfies_kind=None, seed=0):
     """dataset_readers.py:476-509. The point cloud is SOURCE/points3d.ply if present; otherwise points.npy as
-    (xyz - center) * scale with colours SH2RGB(U[0, 1) / 255) from a seeded generator, written to
-    MODEL/input.ply when model_path is given (never under SOURCE) and read back from there, so the colours
-    carry the file's 8-bit rounding as upstream."""
+    (xyz - center) * scale with colours SH2RGB(U[0, 1) / 255) from a seeded generator (start_point_cloud)."""
     cams, train_num, scene_center, scene_scale = read_nerfies_cameras(path, nerfies_kind)
     train, test = (cams[:train_num], cams[train_num:]) if eval else (cams, [])
     norm = nerfpp_norm(train)
-    ply_path = os.path.join(path, "points3d.ply")
-    npy_path = os.path.join(path, "points.npy")
-    if os.path.exists(ply_path):
-        pcd = fetch_ply(ply_path)
-    elif os.path.exists(npy_path):
+
+    def points():
+        npy_path = os.path.join(path, "points.npy")
+        if not os.path.exists(npy_path):
+            raise ValueError(f"{path}: neither points3d.ply nor points.npy (a Nerfies dataset brings its point cloud)")
         xyz = (np.load(npy_path) - scene_center) * scene_scale
         rgb = np.random.default_rng(seed).random((xyz.shape[0], 3)) / 255.0 * C0 + 0.5
-        ply_path = None
-        if model_path:
-            os.makedirs(model_path, exist_ok=True)
-            ply_path = os.path.join(model_path, "input.ply")
-            store_ply(ply_path, xyz, rgb * 255)
-            pcd = fetch_ply(ply_path)
-        else:
-            pcd = BasicPointCloud(points=xyz.astype(np.float32), colors=(rgb * 255).astype(np.uint8) / 255.0,
-                                  normals=np.zeros((xyz.shape[0], 3)))
-    else:
-        raise ValueError(f"{path}: neither points3d.ply nor points.npy (a Nerfies dataset brings its point cloud)")
+        return xyz, rgb * 255
+
+    pcd, ply_path = start_point_cloud(os.path.join(path, "points3d.ply"), points, model_path)
     return SceneInfo(point_cloud=pcd, train_cameras=train, test_cameras=test, nerf_normalization=norm, ply_path=ply_path)
 
 
@@ -468,9 +485,8 @@ def read_colmap_cameras(path, images=None):
         except ValueError:
             raise ValueError(f"{pair[0]}: image name {extr.name!r}: a Colmap image must be named by its frame number "
                              "(the frame time is int(name) / (images - 1))") from None
-        with open(image_path, "rb") as f:
-            head = f.read(26)
-        if head[:8] == b"\x89PNG\r\n\x1a\n" and len(head) == 26 and head[25] in (4, 6):
+        fmt, _, _, colour_type = _header(image_path)
+        if fmt == "png" and colour_type in (4, 6):
             raise ValueError(f"{image_path}: an image with an alpha channel in a Colmap directory (gt_alpha_mask) is unsupported")
         infos.append(CameraInfo(uid=intr.id, R=R, T=T, FovY=fovy, FovX=fovx, image_path=image_path, image_name=image_name,
                                 width=intr.width, height=intr.height, fid=number / (num_frames - 1)))
@@ -479,8 +495,7 @@ def read_colmap_cameras(path, images=None):
 
 def read_colmap(path, eval, images=None, model_path=None, llffhold=8):
     """dataset_readers.py:172-220. The point cloud is sparse/0/points3D.ply if present; otherwise points3D.bin,
-    else points3D.txt, written to MODEL/input.ply when model_path is given (the reference writes
-    sparse/0/points3D.ply; SOURCE is never written here) and read back from there."""
+    else points3D.txt (start_point_cloud; the reference writes the converted cloud to sparse/0/points3D.ply)."""
     cams = sorted(read_colmap_cameras(path, images), key=lambda c: c.image_name)  # as strings: "10" < "2"
     if eval:
         train = [c for i, c in enumerate(cams) if i % llffhold != 0]
@@ -489,25 +504,14 @@ def read_colmap(path, eval, images=None, model_path=None, llffhold=8):
         train, test = cams, []
     norm = nerfpp_norm(train)
     sparse = os.path.join(path, "sparse", "0")
-    ply_path = os.path.join(sparse, "points3D.ply")
-    if os.path.exists(ply_path):
-        pcd = fetch_ply(ply_path)
-    else:
+
+    def points():
         for name in ("points3D.bin", "points3D.txt"):
             if os.path.isfile(os.path.join(sparse, name)):
-                xyz, rgb = read_colmap_points(os.path.join(sparse, name))
-                break
-        else:
-            raise ValueError(f"{path}: no sparse/0/points3D.ply, .bin or .txt (a Colmap dataset brings its point cloud)")
-        ply_path = None
-        if model_path:
-            os.makedirs(model_path, exist_ok=True)
-            ply_path = os.path.join(model_path, "input.ply")
-            store_ply(ply_path, xyz, rgb)
-            pcd = fetch_ply(ply_path)
-        else:
-            pcd = BasicPointCloud(points=xyz.astype(np.float32), colors=rgb.astype(np.uint8) / 255.0,
-                                  normals=np.zeros((xyz.shape[0], 3), np.float32))
+                return read_colmap_points(os.path.join(sparse, name))
+        raise ValueError(f"{path}: no sparse/0/points3D.ply, .bin or .txt (a Colmap dataset brings its point cloud)")
+
+    pcd, ply_path = start_point_cloud(os.path.join(sparse, "points3D.ply"), points, model_path, np.float32)
     return SceneInfo(point_cloud=pcd, train_cameras=train, test_cameras=test, nerf_normalization=norm, ply_path=ply_path)
 
 
@@ -534,6 +538,19 @@ def dataset_format(source_path):
                              "(D-NeRF and Nerfies directories are read)")
     raise ValueError(f"{source_path}: could not recognise the scene type (no transforms_train.json of a D-NeRF "
                      "directory and no dataset.json of a Nerfies one)")
+
+
+def render_format(source_path):
+    """The render script's reader of SOURCE, on the same markers: "Colmap" where sparse/ exists (with
+    dataset_format's refusal of an unreadable sparse/0), "Nerfies" for a dataset.json without a
+    transforms_train.json, and "D-NeRF", the transforms reader, for everything else. The two rules differ where
+    training refuses: a DTU, plenoptic or Dynamic-360 marker, or no marker at all (one transforms_test.json, an
+    empty directory), is a ValueError of dataset_format and the transforms reader here, which takes whichever of
+    the two transforms files exist and yields empty sets for the others."""
+    found = {name for marker, name in _FORMAT_MARKERS if os.path.exists(os.path.join(source_path, marker))}
+    if "Colmap" in found:
+        return dataset_format(source_path)  # sparse is the first marker: "Colmap", or the refusal
+    return "Nerfies" if "Nerfies" in found and "D-NeRF" not in found else "D-NeRF"
 
 
 def read_scene_info(source_path, white_background, eval, init_points=100_000, model_path=None, nerfies_kind=None,
@@ -573,20 +590,25 @@ def camera_to_json(id, cam):
             "fy": fov2focal(cam.FovY, cam.height), "fx": fov2focal(cam.FovX, cam.width)}
 
 
-def load_cameras(cam_infos, resolution, white_background, device):
-    """camera_utils.py:60-66 cameraList_from_camInfos: one ingest batch for the set, one Camera per view."""
-    from .ingest import ingest_images
+def load_cameras(cam_infos, resolution, white_background, device, size=None):
+    """camera_utils.py:60-66 cameraList_from_camInfos: one ingest batch for the set, one Camera per view.
+    size None: the -r rule (target_resolution) on the files' own size; every view has its image. size (W, H),
+    the render script's forced frame size: views whose image file exists carry it resized to that (byte / 255,
+    which an 8-bit write maps back to the same byte), the others stay without original_image."""
     if not cam_infos:
         return []
-    images = ingest_images([c.image_path for c in cam_infos], white_background,
-                           size=lambda w, h: target_resolution(w, h, resolution), device=device)
+    have = [i for i, c in enumerate(cam_infos) if size is None or (c.image_path and os.path.isfile(c.image_path))]
+    if have:
+        images = ingest_images([cam_infos[i].image_path for i in have], white_background, device=device,
+                               size=size or (lambda w, h: target_resolution(w, h, resolution)))
+    width, height = size or (images.shape[3], images.shape[2])
     cams = []
     for i, c in enumerate(cam_infos):
-        cam = Camera(c.R, c.T, FoVx=c.FovX, FoVy=c.FovY, width=images.shape[3], height=images.shape[2], fid=c.fid,
-                     uid=i, data_device=device)
-        cam.original_image = images[i]
+        cam = Camera(c.R, c.T, FoVx=c.FovX, FoVy=c.FovY, width=width, height=height, fid=c.fid, uid=i, data_device=device)
         cam.image_name = c.image_name
         cams.append(cam)
+    for k, i in enumerate(have):
+        cams[i].original_image = images[k]
     return cams
 
 

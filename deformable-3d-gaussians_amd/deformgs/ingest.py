@@ -132,31 +132,19 @@ def _read(item):
         return f.read()
 
 
-def inflate_all(items, threads=MAX_INFLATE_THREADS):
-    """-> [(W, H, channels, filtered scanlines)] in input order; validated. At most 16 inflate threads."""
-    def one(item):
-        w, h, ch, raw = inflate_png(_read(item))
-        if ch not in (3, 4):
-            raise ValueError(f"ingest_images takes RGB or RGBA images, got {ch} channel(s)")
-        validate_scanlines(raw, w, h, ch)
-        return w, h, ch, raw
-    n = max(1, min(int(threads), MAX_INFLATE_THREADS, len(items)))
-    if n == 1:
-        return [one(it) for it in items]
-    with ThreadPoolExecutor(max_workers=n) as pool:
-        return list(pool.map(one, items))
-
-
 PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
 
 
-def image_format(data):
-    """"png" or "jpeg" from the first bytes of the file."""
-    if data[:8] == PNG_SIGNATURE:
-        return "png"
-    if data[:2] == b"\xff\xd8":
-        return "jpeg"
-    raise ValueError("ingest_images takes PNG or JPEG files (neither signature found)")
+def image_header(head):
+    """The first 26 bytes of a file (more do no harm) -> (format, width, height, colour type). "png": the IHDR's
+    size, or None where the bytes are short of it or hold no IHDR there, and its colour type byte (None when
+    short). "jpeg": None for the rest, its size lies behind its markers (jpeg.jpeg_size). Neither signature:
+    format None. The callers word their own refusals."""
+    if head[:8] == PNG_SIGNATURE:
+        ihdr = len(head) >= 24 and head[12:16] == b"IHDR"
+        return ("png", int.from_bytes(head[16:20], "big") if ihdr else None,
+                int.from_bytes(head[20:24], "big") if ihdr else None, head[25] if len(head) >= 26 else None)
+    return "jpeg" if head[:2] == b"\xff\xd8" else None, None, None, None
 
 
 def _pool_map(fn, items, threads):
@@ -169,11 +157,14 @@ def _pool_map(fn, items, threads):
 
 def front_end_all(items, native_jpeg, threads=MAX_INFLATE_THREADS):
     """-> [(format, W, H, channels or (hs, vs), payload)] in input order. PNG: payload = the validated filtered
-    scanlines (inflate_all). JPEG: only the header is read here; payload = (file bytes, header), the header
+    scanlines. JPEG: only the header is read here; payload = (file bytes, header), the header
     being a _lib.JpegInfo (native_jpeg: the C++ front end) or a jpeg.JpegHeader (the Python one)."""
     def one(item):
         data = _read(item)
-        if image_format(data) == "png":
+        fmt = image_header(data)[0]
+        if fmt is None:
+            raise ValueError("ingest_images takes PNG or JPEG files (neither signature found)")
+        if fmt == "png":
             w, h, ch, raw = inflate_png(data)
             if ch not in (3, 4):
                 raise ValueError(f"ingest_images takes RGB or RGBA images, got {ch} channel(s)")
@@ -282,55 +273,56 @@ def _target(size, W, H):
     return int(w), int(h)
 
 
+def resize_float_device(rgb8, size, out=None):
+    """Steps 3-4 on the device, the tail of every group: uint8 (B, H, W, 3) -> horizontal pass, vertical pass (a
+    pass whose axis keeps its size is skipped) -> float, on the current stream. -> (float (B, 3, h, w), uint8
+    (B, h, w, 3)). `out`: a (B, 3, h, w) float view to fill."""
+    w, h = size
+    if w != rgb8.shape[2]:
+        rgb8 = _resample_device(rgb8, 2, w)
+    if h != rgb8.shape[1]:
+        rgb8 = _resample_device(rgb8, 1, h)
+    if out is None:
+        out = torch.empty((rgb8.shape[0], 3, h, w), dtype=torch.float32, device=rgb8.device)
+    _to_float_device(rgb8, out)
+    return out, rgb8
+
+
+def resize_float_numpy(px, size):
+    """Steps 3-4 in numpy: uint8 (B, H, W, 3) -> (float32 (B, 3, h, w), uint8 (B, h, w, 3)) arrays."""
+    rgb8 = np.ascontiguousarray(resize_numpy(px, size))
+    return np.ascontiguousarray(rgb8.transpose(0, 3, 1, 2)).astype(np.float32) / np.float32(255.0), rgb8
+
+
 def ingest_group_device(raws, W, H, channels, white_background, size, device, out=None, lut=None):
     """One (W, H, channels) group on the device: one upload, then unfilter (+ composite) -> resize -> float on
-    the current stream. -> (float (B, 3, h, w), uint8 (B, h, w, 3)). `out`: a (B, 3, h, w) float view to fill."""
-    B = len(raws)
-    w, h = size
+    the current stream. -> (float (B, 3, h, w), uint8 (B, h, w, 3)). `out`: a (B, 3, h, w) float view to fill.
+    `lut`: the composite table already on the device; without one an RGBA group uploads its own."""
     host = torch.from_numpy(np.frombuffer(b"".join(raws), np.uint8).copy())
     scan = host.to(device)
     if channels == 4 and lut is None:
         lut = torch.from_numpy(composite_table(white_background).reshape(-1).copy()).to(device)
-    rgb8 = unfilter_device(scan, B, W, H, channels, lut if channels == 4 else None)
-    if w != W:
-        rgb8 = _resample_device(rgb8, 2, w)
-    if h != H:
-        rgb8 = _resample_device(rgb8, 1, h)
-    if out is None:
-        out = torch.empty((B, 3, h, w), dtype=torch.float32, device=device)
-    _to_float_device(rgb8, out)
-    return out, rgb8
+    return resize_float_device(unfilter_device(scan, len(raws), W, H, channels, lut if channels == 4 else None), size, out)
 
 
 def ingest_jpeg_group_device(files, W, H, sampling, size, device, out=None, threads=MAX_INFLATE_THREADS):
     """One (W, H, sampling) group of JPEG files [(bytes, _lib.JpegInfo)] on the device: threaded Huffman
     decode into one host buffer, two uploads, IDCT + upsampling + colour, then resize -> float as for PNG.
     -> (float (B, 3, h, w), uint8 (B, h, w, 3))."""
-    w, h = size
     coef, qt = jpeg_decode_host(files, threads)
-    rgb8 = jpeg_device(coef, qt, W, H, sampling[0], sampling[1], device)
-    if w != W:
-        rgb8 = _resample_device(rgb8, 2, w)
-    if h != H:
-        rgb8 = _resample_device(rgb8, 1, h)
-    if out is None:
-        out = torch.empty((len(files), 3, h, w), dtype=torch.float32, device=device)
-    _to_float_device(rgb8, out)
-    return out, rgb8
+    return resize_float_device(jpeg_device(coef, qt, W, H, sampling[0], sampling[1], device), size, out)
 
 
 def ingest_jpeg_group_numpy(files, size):
     """The same in Python and numpy (deformgs/jpeg.py). files: [(bytes, jpeg.JpegHeader)]."""
     px = np.stack([jpeg.upsample_color(jpeg.idct_planes(jpeg.decode_coefficients(d, hd), hd), hd) for d, hd in files])
-    rgb8 = np.ascontiguousarray(resize_numpy(px, size))
-    return np.ascontiguousarray(rgb8.transpose(0, 3, 1, 2)).astype(np.float32) / np.float32(255.0), rgb8
+    return resize_float_numpy(px, size)
 
 
 def ingest_group_numpy(raws, W, H, channels, white_background, size):
     """The same steps in numpy. -> (float32 (B, 3, h, w), uint8 (B, h, w, 3)) arrays."""
     px = np.stack([unfilter(r, W, H, channels) for r in raws])
-    rgb8 = np.ascontiguousarray(resize_numpy(composite_numpy(px, white_background), size))
-    return np.ascontiguousarray(rgb8.transpose(0, 3, 1, 2)).astype(np.float32) / np.float32(255.0), rgb8
+    return resize_float_numpy(composite_numpy(px, white_background), size)
 
 
 def ingest_images(images, white_background, size=None, device="cuda", return_uint8=False, threads=MAX_INFLATE_THREADS):
@@ -355,7 +347,6 @@ def ingest_images(images, white_background, size=None, device="cuda", return_uin
     w, h = next(iter(targets))
     out = torch.empty((len(images), 3, h, w), dtype=torch.float32, device=dev)
     out8 = torch.empty((len(images), h, w, 3), dtype=torch.uint8, device=dev) if return_uint8 else None
-    lut = None
     for (fmt, W, H, ch), idx in groups.items():
         raws = [metas[i][4] for i in idx]
         whole = len(groups) == 1  # then the group's result is the output itself
@@ -363,9 +354,7 @@ def ingest_images(images, white_background, size=None, device="cuda", return_uin
             if fmt == "jpeg":
                 f, u = ingest_jpeg_group_device(raws, W, H, ch, (w, h), dev, out if whole else None, threads)
             else:
-                if ch == 4 and lut is None:
-                    lut = torch.from_numpy(composite_table(white_background).reshape(-1).copy()).to(dev)
-                f, u = ingest_group_device(raws, W, H, ch, white_background, (w, h), dev, out if whole else None, lut)
+                f, u = ingest_group_device(raws, W, H, ch, white_background, (w, h), dev, out if whole else None)
         else:
             if fmt == "jpeg":
                 f, u = ingest_jpeg_group_numpy(raws, (w, h))

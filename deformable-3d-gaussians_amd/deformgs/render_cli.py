@@ -26,16 +26,13 @@ size. -s SOURCE at a Colmap directory (sparse/0) does the same through deformgs/
 sorted by name, every 8th the test set, images from -i / --images (default images).
 """
 import argparse
-import json
-import math
 import os
 import time
 
-import numpy as np
 import torch
 
 from .camera_paths import DIR_NAMES, MODES, frame_list
-from .cameras import Camera, blender_c2w_to_RT, focal2fov, fov2focal
+from .cameras import Camera
 from .png import write_png
 
 
@@ -44,76 +41,32 @@ class _Set:
         self.train, self.test = train, test
 
 
-def attach_images(cams, paths, white_background, width, height, device):
-    """Views whose image file exists get original_image: composited over the background and resized to the
-    render size by deformgs/ingest.py (byte / 255, which render_set's 8-bit gt/ write maps back to the same
-    byte). The others stay without one."""
-    from .ingest import ingest_images
-    have = [i for i, p in enumerate(paths) if p and os.path.isfile(p)]
-    if not have:
-        return
-    images = ingest_images([paths[i] for i in have], white_background, size=(width, height), device=device)
-    for k, i in enumerate(have):
-        cams[i].original_image = images[k]
-
-
 def read_transforms(source, width, height, device, white_background=False, extension=".png"):
-    """D-NeRF transforms_{train,test}.json -> _Set of Cameras (dataset_readers.py:222-262); a view carries its
-    ground-truth image when the frame's file exists under `source`."""
-    sets = {}
-    for name in ("train", "test"):
-        path = os.path.join(source, f"transforms_{name}.json")
-        cams, files = [], []
-        if os.path.exists(path):
-            with open(path) as f:
-                meta = json.load(f)
-            fovx = float(meta["camera_angle_x"])
-            frames = meta["frames"]
-            for k, fr in enumerate(frames):
-                R, T = blender_c2w_to_RT(np.array(fr["transform_matrix"]))
-                fovy = focal2fov(fov2focal(fovx, width), height)
-                fid = float(fr["time"]) if "time" in fr else k / max(len(frames) - 1, 1)
-                # dataset_readers.py:260-262 swaps the names: FovY = fovx, FovX = fovy
-                cams.append(Camera(R, T, FoVx=fovy, FoVy=fovx, width=width, height=height, fid=fid, uid=k,
-                                   data_device=device))
-                files.append(os.path.join(source, fr["file_path"] + extension) if "file_path" in fr else None)
-            attach_images(cams, files, white_background, width, height, device)
-        sets[name] = cams
-    return _Set(sets["train"], sets["test"])
-
-
-def read_nerfies_sets(source, res, resolution, device, nerfies_kind=None):
-    """A Nerfies directory -> _Set of Cameras with their ground truth, split as the training reader splits it with
-    --eval. res None: the files' size after the -r rule (dataset.load_cameras); (W, H): that frame size."""
-    from .dataset import load_cameras, read_nerfies_cameras
-    infos, train_num, _, _ = read_nerfies_cameras(source, nerfies_kind)
+    """D-NeRF transforms_{train,test}.json -> _Set of Cameras (dataset_readers.py:222-262) at the given frame
+    size; a missing file is an empty set, a frame without `time` takes k / (n - 1), and a view carries its
+    ground-truth image (composited over the background) when the frame's file exists under `source`."""
+    from .dataset import load_cameras, transforms_camera, transforms_frames
     sets = []
-    for part in (infos[:train_num], infos[train_num:]):
-        if res is None:
-            sets.append(load_cameras(part, resolution, False, device))
-            continue
-        cams = [Camera(c.R, c.T, FoVx=c.FovX, FoVy=c.FovY, width=res[0], height=res[1], fid=c.fid, uid=k,
-                       data_device=device) for k, c in enumerate(part)]
-        attach_images(cams, [c.image_path for c in part], False, res[0], res[1], device)
-        sets.append(cams)
+    for name in ("transforms_train.json", "transforms_test.json"):
+        frames = transforms_frames(source, name, extension) if os.path.exists(os.path.join(source, name)) else []
+        infos = [transforms_camera(k, R, T, float(fovx), k / max(len(frames) - 1, 1) if t is None else float(t),
+                                   image_path, width, height) for k, (R, T, fovx, t, image_path) in enumerate(frames)]
+        sets.append(load_cameras(infos, None, white_background, device, size=(width, height)))
     return _Set(*sets)
 
 
-def read_colmap_sets(source, res, resolution, device, images=None):
-    """A Colmap directory -> _Set of Cameras with their ground truth, split as the training reader splits it with
-    --eval (every 8th camera by name is the test set). res as for read_nerfies_sets."""
-    from .dataset import load_cameras, read_colmap
-    info = read_colmap(source, True, images=images)
-    sets = []
-    for part in (info.train_cameras, info.test_cameras):
-        if res is None:
-            sets.append(load_cameras(part, resolution, False, device))
-            continue
-        cams = [Camera(c.R, c.T, FoVx=c.FovX, FoVy=c.FovY, width=res[0], height=res[1], fid=c.fid, uid=k,
-                       data_device=device) for k, c in enumerate(part)]
-        attach_images(cams, [c.image_path for c in part], False, res[0], res[1], device)
-        sets.append(cams)
-    return _Set(*sets)
+def read_dataset_sets(source, fmt, res, resolution, device, nerfies_kind=None, images=None):
+    """A "Nerfies" or "Colmap" directory -> _Set of Cameras with their ground truth, split as the training reader
+    splits it with --eval (Nerfies: train ids, then val ids; Colmap: every 8th camera by name is the test set).
+    res None: the files' size after the -r rule; (W, H): that frame size (dataset.load_cameras)."""
+    from .dataset import load_cameras, read_colmap, read_nerfies_cameras
+    if fmt == "Colmap":
+        info = read_colmap(source, True, images=images)
+        parts = info.train_cameras, info.test_cameras
+    else:
+        infos, train_num, _, _ = read_nerfies_cameras(source, nerfies_kind)
+        parts = infos[:train_num], infos[train_num:]
+    return _Set(*(load_cameras(part, resolution, False, device, size=res) for part in parts))
 
 
 def _iteration(model_path, iteration):
@@ -145,15 +98,13 @@ def load_scene(args, device="cuda"):
                     head.weight.mul_(0.01)
                     head.bias.mul_(0.01)
             d0.save_weights(args.model_path, 0)
-    elif args.source_path and os.path.exists(os.path.join(args.source_path, "sparse")):
-        from .dataset import dataset_format
-        dataset_format(args.source_path)  # raises on a sparse/ without a readable sparse/0 model
-        cams = read_colmap_sets(args.source_path, args.res, args.resolution, dev, args.images)
-    elif args.source_path and os.path.exists(os.path.join(args.source_path, "dataset.json")) and not os.path.exists(
-            os.path.join(args.source_path, "transforms_train.json")):
-        cams = read_nerfies_sets(args.source_path, args.res, args.resolution, dev, args.nerfies_kind)
     elif args.source_path:
-        cams = read_transforms(args.source_path, W, H, dev, white_background=args.white_background)
+        from .dataset import render_format
+        fmt = render_format(args.source_path)
+        if fmt == "D-NeRF":
+            cams = read_transforms(args.source_path, W, H, dev, white_background=args.white_background)
+        else:
+            cams = read_dataset_sets(args.source_path, fmt, args.res, args.resolution, dev, args.nerfies_kind, args.images)
     else:
         raise SystemExit("render_cli: give the cameras with --synthetic N or -s SOURCE (transforms_*.json)")
     it = _iteration(args.model_path, args.iteration)
@@ -191,6 +142,12 @@ def _write_video(path, rgb, fps, chunk, quality, subsampling):
     write_avi(path, jpegs, rgb.shape[2], rgb.shape[1], fps)
 
 
+def _gt8(cams):
+    """The views' ground truth as the bytes gt/ holds: uint8 (n, H, W, 3) on the images' device."""
+    gt = torch.stack([c.original_image[0:3] for c in cams])
+    return (255 * gt.clamp(0, 1)).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+
+
 def _write_gpu(out, cams, dirs, chunk):
     """--png gpu: renders, depth and the 8-bit ground truth go through deformgs.png_gpu in chunks of frames; only
     compressed bytes reach the host."""
@@ -205,9 +162,7 @@ def _write_gpu(out, cams, dirs, chunk):
         if "gt" in dirs:
             have = [i for i in idx if getattr(cams[i], "original_image", None) is not None]
             if have:
-                gt = torch.stack([cams[i].original_image[0:3] for i in have])
-                gt8 = (255 * gt.clamp(0, 1)).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
-                write_frames([os.path.join(dirs["gt"], f"{i:05d}.png") for i in have], gt8)
+                write_frames([os.path.join(dirs["gt"], f"{i:05d}.png") for i in have], _gt8([cams[i] for i in have]))
 
 
 def render_set(model_path, name, iteration, mode, views, gaussians, deform, background, is_6dof, view_index=0,
@@ -241,9 +196,7 @@ def render_set(model_path, name, iteration, mode, views, gaussians, deform, back
             write_png(os.path.join(dirs["renders"], f"{i:05d}.png"), rgb[i])
             write_png(os.path.join(dirs["depth"], f"{i:05d}.png"), dep[i])
             if mode == "render" and getattr(cams[i], "original_image", None) is not None:
-                gt = cams[i].original_image[0:3]
-                gt8 = (255 * gt.clamp(0, 1)).to(torch.uint8).permute(1, 2, 0).contiguous().cpu().numpy()
-                write_png(os.path.join(dirs["gt"], f"{i:05d}.png"), gt8)
+                write_png(os.path.join(dirs["gt"], f"{i:05d}.png"), _gt8([cams[i]])[0].cpu().numpy())
     if video == "mjpeg" and mode in VIDEO_FPS and cams:
         _write_video(os.path.join(dirs["renders"], "video.avi"), out["rgb8"], VIDEO_FPS[mode], chunk, video_quality,
                      video_subsampling)

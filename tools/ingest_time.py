@@ -4,7 +4,7 @@
 The images are rendered-looking frames (tests/png_fixtures.disc_image; --distinct of them, repeated), encoded
 with adaptive per-row filters (the libpng heuristic), so Paeth and Average rows dominate as in real renders.
 Timed, medians of --rounds rounds, the legs alternating within a round:
-  (a) host inflate + validation, at most 16 threads (deformgs.ingest.inflate_all)
+  (a) host inflate + validation, at most 16 threads (deformgs.ingest.front_end_all, the front end of ingest_images)
   (b) upload + HIP ingest to the float images at 800^2 and at 400^2 (ends in a device synchronise)
   (c) the numpy path on 5 of the images, scaled to the full count
   (d) where PIL is importable: the reference's pipeline per image: Image.open().convert("RGBA"), the float64
@@ -102,14 +102,7 @@ def jpeg_main(args):
     full, half = (W, H), (W // 2, H // 2)
 
     def device_leg(coef, qt, size):
-        rgb8 = ingest.jpeg_device(coef, qt, W, H, hs, vs, dev)
-        if size[0] != W:
-            rgb8 = ingest._resample_device(rgb8, 2, size[0])
-        if size[1] != H:
-            rgb8 = ingest._resample_device(rgb8, 1, size[1])
-        out = torch.empty((coef.shape[0], 3, size[1], size[0]), dtype=torch.float32, device=dev)
-        ingest._to_float_device(rgb8, out)
-        return out
+        return ingest.resize_float_device(ingest.jpeg_device(coef, qt, W, H, hs, vs, dev), size)[0]
 
     coef, qt = ingest.jpeg_decode_host(files)
     for size in (full, half):  # warm-up of every timed shape
@@ -179,8 +172,7 @@ def main():
         have_pil = True
     except ImportError:
         have_pil = False
-    metas = ingest.inflate_all(pngs)
-    raws = [m[3] for m in metas]
+    raws = [m[4] for m in ingest.front_end_all(pngs, True)]
     # warm-up of every timed shape; the small result is also checked against the numpy path
     for size in (full, half):
         f, _ = ingest.ingest_group_device(raws[:8], W, H, ch, False, size, dev)
@@ -190,7 +182,7 @@ def main():
     t = {k: [] for k in ("inflate", "hip_full", "hip_half", "numpy_half", "pil_half")}
     for _ in range(args.rounds):
         t0 = time.perf_counter()
-        ingest.inflate_all(pngs)
+        ingest.front_end_all(pngs, True)
         t["inflate"].append(time.perf_counter() - t0)
         for key, size in (("hip_full", full), ("hip_half", half)):
             torch.cuda.synchronize()
