@@ -58,6 +58,7 @@ __device__ __forceinline__ void level_terms(float m0, float m1, float e00, float
 // One 32x32 tile of one plane. VALID = false: zero-padded 'same' filter (the loss's SSIM) ->
 // partial = (sum (x-y)^2, sum ssim). VALID = true: unpadded filter of an MS-SSIM level ->
 // partial = (sum cs, sum ssim) over the (h-10) x (w-10) outputs. partial: [plane][tile y][tile x][2].
+// The tap sums are explicit fmaf, as k_ssim_fwd's (ssim.hip says why): the two stay bit for bit alike.
 template <bool VALID>
 __global__ __launch_bounds__(256) void k_tile(int h, int w, const float *__restrict__ X, const float *__restrict__ Y,
                                               Win win, float *__restrict__ partial) {
@@ -93,11 +94,11 @@ __global__ __launch_bounds__(256) void k_tile(int h, int w, const float *__restr
 #pragma unroll
             for (int k = 0; k < 11; k++) {
                 const float i = a[j + k], g = b[j + k], wk = win.w[k];
-                m0 += wk * i;
-                m1 += wk * g;
-                m2 += wk * (i * i);
-                m3 += wk * (g * g);
-                m4 += wk * (i * g);
+                m0 = fmaf(wk, i, m0);
+                m1 = fmaf(wk, g, m1);
+                m2 = fmaf(wk, i * i, m2);
+                m3 = fmaf(wk, g * g, m3);
+                m4 = fmaf(wk, i * g, m4);
             }
             hq[0][ly][lx0 + j] = m0; hq[1][ly][lx0 + j] = m1; hq[2][ly][lx0 + j] = m2;
             hq[3][ly][lx0 + j] = m3; hq[4][ly][lx0 + j] = m4;
@@ -116,7 +117,7 @@ __global__ __launch_bounds__(256) void k_tile(int h, int w, const float *__restr
         for (int j = 0; j < VY; j++) {
             float acc = 0.f;
 #pragma unroll
-            for (int k = 0; k < 11; k++) acc += win.w[k] * v[j + k];
+            for (int k = 0; k < 11; k++) acc = fmaf(win.w[k], v[j + k], acc);
             mu[m][j] = acc;
         }
     }

@@ -25,6 +25,9 @@ namespace ssim {
 // forward: 5 maps (mu1, mu2, E[I^2], E[G^2], E[IG]); the products are formed on the fly from the two
 // input tiles. Row pass: each item = one tile row x 8 columns from 18 inputs held in registers;
 // column pass: each thread slides 14 row-filtered values down one column for 4 outputs.
+// Every tap of both passes is an explicit fmaf: left to contraction, the compiler vectorised the
+// E[I^2] / E[G^2] sums in pairs and kept E[IG] scalar, and the two were not fused alike, so that with
+// I == G the three maps differed in their last bits and SSIM of an identical pair was not exactly 1.
 // block (tile) partial sums: [blocks][2] = (sum |I-G|, sum ssim)
 __global__ __launch_bounds__(256) void k_ssim_fwd(int H, int W, const float *__restrict__ I, const float *__restrict__ G,
                                                   Win win, float *__restrict__ maps, float *__restrict__ partial) {
@@ -52,11 +55,11 @@ __global__ __launch_bounds__(256) void k_ssim_fwd(int H, int W, const float *__r
 #pragma unroll
             for (int k = 0; k < 11; k++) {
                 const float i = a[j + k], g = b[j + k], w = win.w[k];
-                m0 += w * i;
-                m1 += w * g;
-                m2 += w * (i * i);
-                m3 += w * (g * g);
-                m4 += w * (i * g);
+                m0 = fmaf(w, i, m0);
+                m1 = fmaf(w, g, m1);
+                m2 = fmaf(w, i * i, m2);
+                m3 = fmaf(w, g * g, m3);
+                m4 = fmaf(w, i * g, m4);
             }
             hq[0][ly][lx0 + j] = m0; hq[1][ly][lx0 + j] = m1; hq[2][ly][lx0 + j] = m2;
             hq[3][ly][lx0 + j] = m3; hq[4][ly][lx0 + j] = m4;
@@ -75,7 +78,7 @@ __global__ __launch_bounds__(256) void k_ssim_fwd(int H, int W, const float *__r
         for (int j = 0; j < VY; j++) {
             float acc = 0.f;
 #pragma unroll
-            for (int k = 0; k < 11; k++) acc += win.w[k] * v[j + k];
+            for (int k = 0; k < 11; k++) acc = fmaf(win.w[k], v[j + k], acc);
             mu[m][j] = acc;
         }
     }

@@ -63,18 +63,25 @@ __device__ __forceinline__ void load_tile(float (*sm)[S][SP], const float *const
 }
 
 // SSIM of one pixel of the zero-padded filter from its five filtered maps: sv = n1 n2 / (d1 d2), with
-// the factors the loss's backward coefficients are built from
+// the factors the loss's backward coefficients are built from. Every operation is rounded on its own
+// (no contraction: mu1^2 + mu2^2 as fma(mu1, mu1, round(mu2^2)) is not 2 round(mu1 mu2)) and sv is one
+// correctly rounded division of the two products, as the reference evaluates it, not n1 n2 inv: with
+// identical inputs (and the kernels' five sums formed alike, by explicit fmaf) n1 == d1 and n2 == d2
+// bit for bit, every pixel is exactly 1.0, the tile sums are exact and the mean SSIM is 1.0, as the
+// reference's (tests/test_gpu_loss_parity.py, `identical`; it was 2-3 ulps below)
 struct Pixel {
     float n1, n2, d1, d2, inv, sv;
 };
 __device__ __forceinline__ Pixel ssim_pixel(float mu1, float mu2, float e11, float e22, float e12) {
+#pragma clang fp contract(off)
     const float mu1s = mu1 * mu1, mu2s = mu2 * mu2, mu12 = mu1 * mu2;
     const float s11 = e11 - mu1s, s22 = e22 - mu2s, s12 = e12 - mu12;
     Pixel p;
     p.n1 = 2.f * mu12 + C1, p.n2 = 2.f * s12 + C2;
     p.d1 = mu1s + mu2s + C1, p.d2 = s11 + s22 + C2;
-    p.inv = 1.f / (p.d1 * p.d2);
-    p.sv = p.n1 * p.n2 * p.inv;
+    const float d12 = p.d1 * p.d2;
+    p.inv = 1.f / d12;
+    p.sv = (p.n1 * p.n2) / d12;
     return p;
 }
 

@@ -1,6 +1,9 @@
 """Fused HIP L1+SSIM (dgs_l1_ssim_*) vs the reference's own loss (golden) and the torch mirror.
-Tolerance: loss / L1 / SSIM values to 1e-6 abs; dL/dimg to 1e-6 relative to its max (fp32 sums in a
-different order than MIOpen's conv)."""
+Tolerance: loss / L1 / SSIM values to 1e-6 abs (2e-6 against the torch mirror); dL/dimg to 1e-5 relative to its max
+(fp32 sums in a different order than the mirror's conv). These fixed bars hold for the inputs of this file only (the
+golden pair, uniform noise): on a render close to a target on a white background the reference's own fp32 SSIM is
+already 1e-5 from float64. tests/test_gpu_loss_parity.py covers that regime with bars relative to that error, per
+region, against float64."""
 import numpy as np
 import pytest
 import torch

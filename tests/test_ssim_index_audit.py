@@ -32,6 +32,17 @@ def test_ssim_addresses_in_bounds(exe):
     assert r.stdout.count("0 out of bounds") == len(shapes), r.stdout
 
 
+def test_loss_parity_shapes_in_bounds(exe):
+    # tests/test_gpu_loss_parity.py (loss_ref.SHAPES as (C, H, W)): narrower than the window, tile edges +-1, the halo
+    # on a tile edge, 1026 tile blocks for k_ssim_final's strided loop, C = 1 and 4
+    import loss_ref
+    shapes = [(c, h, w) for h, w, c in loss_ref.SHAPES]
+    assert (3, 1, 10913) in shapes and (3, 37, 64) in shapes and (4, 33, 31) in shapes
+    r = subprocess.run([exe] + [str(v) for s in shapes for v in s], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.count("0 out of bounds") == len(shapes), r.stdout
+
+
 def test_metrics_addresses_in_bounds(exe):
     # tests/test_gpu_image_metrics.py: CASES (F, H, W) with three channels -> F * 3 planes; the pyramids'
     # level sizes are fixed here, not taken from the program under test
