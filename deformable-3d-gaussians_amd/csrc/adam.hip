@@ -39,15 +39,19 @@ struct Jobs {
 
 __device__ __forceinline__ void adam1(float &p, float g, float &m, float &v, float c1, float b2, float c2, float eps,
                                       float step_size, float bc2_sqrt) {
-    m = m + c1 * (g - m);
-    v = v * b2 + c2 * (g * g);
+    // the three multiply-adds are stated as fmaf: left to contraction, the element loop rounded b2 v and
+    // c2 g g separately (the compiler paired the two products there) while the float4 loop fused them,
+    // so a tensor's ragged tail or an unaligned tensor got other bits than an aligned one
+    m = fmaf(c1, g - m, m);
+    v = fmaf(v, b2, c2 * (g * g));
     const float denom = sqrtf(v) / bc2_sqrt + eps;
-    p = p + (-step_size) * (m / denom);
+    p = fmaf(-step_size, m / denom, p);
 }
 
 // Each thread updates PER_THREAD / 4 float4 units (16-byte loads and stores of p, g, m, v) when the
 // tensor's four pointers are 16-byte aligned; otherwise (or for a ragged tail) element by element.
-// Same arithmetic per element either way.
+// Same arithmetic per element either way: adam1 leaves the compiler no choice of rounding
+// (tests/test_gpu_adam_parity.py compares the two paths bit for bit).
 __global__ __launch_bounds__(THREADS) void k_adam(Jobs J) {
     const long long b = blockIdx.x;
     int q = 0;
@@ -111,6 +115,15 @@ extern "C" int dgs_adam_step(int n, const dgs_adam_tensor *t, double beta1, doub
         set_error("dgs_adam_step: bad tensor list");
         return DGS_ERR_ARGS;
     }
+    // refuse the whole list before the first launch: a bad entry past the first MAXT jobs must not
+    // leave the earlier tensors stepped
+    for (int i = 0; i < n; i++) {
+        const dgs_adam_tensor &d = t[i];
+        if (d.numel > 0 && (!d.param || !d.grad || !d.exp_avg || !d.exp_avg_sq)) {
+            set_error("dgs_adam_step: null tensor pointer");
+            return DGS_ERR_ARGS;
+        }
+    }
     int k = 0;
     while (k < n) {
         adam::Jobs J{};
@@ -122,10 +135,6 @@ extern "C" int dgs_adam_step(int n, const dgs_adam_tensor *t, double beta1, doub
         for (; k < n && J.n < adam::MAXT; k++) {
             const dgs_adam_tensor &d = t[k];
             if (d.numel <= 0) continue;
-            if (!d.param || !d.grad || !d.exp_avg || !d.exp_avg_sq) {
-                set_error("dgs_adam_step: null tensor pointer");
-                return DGS_ERR_ARGS;
-            }
             adam::Job &j = J.j[J.n++];
             j.p = d.param; j.g = d.grad; j.m = d.exp_avg; j.v = d.exp_avg_sq;
             j.n = d.numel; j.block0 = blocks;

@@ -94,7 +94,8 @@ class Adam(torch.optim.Adam):
 # step_all's launch tables for a fixed set of (parameter, gradient) buffers: a training step with the
 # native step (deformgs/native_step.py) keeps the same gradient buffers every iteration, so after the
 # first step only the step counts and the per-tensor bias corrections change (~40 us of host time
-# instead of ~200 us of per-parameter Python). The cache lives on the first optimizer of the set
+# instead of ~200 us of per-parameter Python). The tables are valid for the buffers (`_signature`), the step
+# counts and every group's (betas, eps) they were built with (`_cfg`); lr is read every step. The cache lives on the first optimizer of the set
 # (`_dgs_fast`) and refers to the others weakly, so it never keeps parameters or Adam moments alive
 # after training; `clear_fast_cache` drops it explicitly.
 
@@ -110,6 +111,15 @@ def clear_fast_cache(*optimizers):
     for o in optimizers:
         if hasattr(o, "_dgs_fast"):
             o._dgs_fast = None
+
+
+def _cfg(group):
+    """The (beta1, beta2, eps) a launch is made with. The cached tables are grouped by it, so the fast path is
+    taken only while every group still has the configuration it was cached with (one tuple compare per group
+    and step: ~1 us for the seven groups of training); a changed group rebuilds the tables, as torch.optim.Adam
+    reads its groups on every step."""
+    b1, b2 = group["betas"]
+    return float(b1), float(b2), float(group["eps"])
 
 
 def _signature(optimizers):
@@ -139,7 +149,8 @@ def step_all(*optimizers):
     sig = _signature(hip)
     fast = _fast_get(hip, key)
     stream = _lib.stream_ptr()
-    if fast is not None and fast["sig"] == sig and all(float(t) == c for t, c in fast["steps"]):
+    if (fast is not None and fast["sig"] == sig and all(float(t) == c for t, c in fast["steps"])
+            and all(_cfg(group) == cfg for group, cfg in fast["cfgs"])):
         counts = {}
         for t, c in fast["steps"]:
             t.fill_(c + 1.0)
@@ -186,5 +197,6 @@ def step_all(*optimizers):
         for (cfg, arr) in launch:
             tables.append((arr, pos[cfg]))
         hip[0]._dgs_fast = {"key": key, "sig": _signature(hip), "steps": [(t, float(t)) for t in steps.values()],
-                            "tables": tables, "launch": launch, "refs": [weakref.ref(o) for o in hip]}
+                            "tables": tables, "launch": launch, "refs": [weakref.ref(o) for o in hip],
+                            "cfgs": [(group, _cfg(group)) for o in hip for group in o.param_groups]}
     del keep
