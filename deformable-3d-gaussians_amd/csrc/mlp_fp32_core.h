@@ -118,14 +118,17 @@ __device__ inline Bias4 load_bias(const float *bias, int n0, int lane) {
     return b;
 }
 
-// acc = relu(acc + bias) in place (the values kept for the deferred store)
+// acc = relu(acc + bias) in place (the values kept for the deferred store). v < 0 ? 0 : v, not fmaxf(v, 0):
+// a NaN stays a NaN as in torch.relu (fmaxf returns the other operand), so a point whose encodings are
+// not finite (|xyz| = inf, or 2^9 |xyz| overflows) comes out non-finite, not as finite garbage
+__device__ __forceinline__ float relu_nan(float v) { return v < 0.f ? 0.f : v; }
 __device__ inline void bias_relu(f32x16 &acc, const Bias4 &b) {
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-        acc[4 * j] = fmaxf(acc[4 * j] + b.v[j].x, 0.f);
-        acc[4 * j + 1] = fmaxf(acc[4 * j + 1] + b.v[j].y, 0.f);
-        acc[4 * j + 2] = fmaxf(acc[4 * j + 2] + b.v[j].z, 0.f);
-        acc[4 * j + 3] = fmaxf(acc[4 * j + 3] + b.v[j].w, 0.f);
+        acc[4 * j] = relu_nan(acc[4 * j] + b.v[j].x);
+        acc[4 * j + 1] = relu_nan(acc[4 * j + 1] + b.v[j].y);
+        acc[4 * j + 2] = relu_nan(acc[4 * j + 2] + b.v[j].z);
+        acc[4 * j + 3] = relu_nan(acc[4 * j + 3] + b.v[j].w);
     }
 }
 

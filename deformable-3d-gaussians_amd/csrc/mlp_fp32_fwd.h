@@ -100,7 +100,7 @@ __global__ __launch_bounds__(256) void k_timenet(FwdArgs a) {
                 const int f = 8 * c + 4 * h;
                 acc += w.x * tin[f] + w.y * tin[f + 1] + w.z * tin[f + 2] + w.w * tin[f + 3];
             }
-        acc = fmaxf(acc, 0.f);
+        acc = relu_nan(acc);
         th[j] = acc;
         a.tc[TC_TH + j] = acc;
     }

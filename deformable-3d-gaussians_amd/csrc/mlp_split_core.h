@@ -62,6 +62,13 @@ __device__ __forceinline__ Scale scale_for(float m) {
     return Scale{pow2f(14 - e), pow2f(e - 14)};
 }
 
+// A bound the split cannot carry: exponent above scale_for's clamp (>= 2^61: the scaled values would
+// overflow f16), an infinity or a NaN (bounds are maxima of float BITS, so a NaN input arrives as the
+// largest). The forward tests the bounds of the inputs it stages (xyz, the t encodings) and poisons such a
+// column tile: all 16 points' outputs are NaN (fwd_block), not the finite values a clamped scale would give
+// the tile's in-range points.
+__device__ __forceinline__ uint32_t bound_bad(float m) { return ((__float_as_uint(m) >> 23) & 255u) > 127u + 60u; }
+
 // hi = f16(a), lo = f16(a - hi) of two (already scaled) values, pairwise: v_cvt_pk_f16_f32, two
 // f16 -> f32, a packed subtraction, v_cvt_pk_f16_f32 (5 VALU per two values)
 __device__ __forceinline__ void hsplit2(float a, float b, uint32_t &h, uint32_t &l) {
@@ -132,6 +139,7 @@ __device__ __forceinline__ void lds_fmax(uint32_t *p, float v) {
 //  bsync[i][q]: block-wide maxima gathered behind a workgroup barrier (staging, narrow timenet tiles)
 //  bmax[L]: max |bias| of trunk layer L (8: heads), from the launch-constant bias table
 //  wstat[L]: max row abs sum of the layer's A image (k_pack's tile statistics; [8]: heads^T)
+//  bad[q]: a staged input bound of column tile q is out of range (bound_bad; forward)
 struct alignas(16) ScaleLDS {
     float ksc[12][4];
     float amax[2][16][4];
@@ -139,6 +147,7 @@ struct alignas(16) ScaleLDS {
     uint32_t bsync[8][4];
     uint32_t bmax[10];
     uint32_t wstat[10];
+    uint32_t bad[4];
 };
 // block-sync slots
 constexpr int BS_XE = 0, BS_TE = 1, BS_TIN = 2, BS_TH = 3, BS_TET = 4, BS_G = 5, BS_GTE = 6;

@@ -225,6 +225,9 @@ __device__ __forceinline__ void fwd_block(const FwdArgs &a, h16x8 *lds, uint32_t
         const float xe_b = fmaxf(1.f, __uint_as_float(sc->bsync[BS_XE][q]));
         sc->ksc[0][q] = sc->ksc[1][q] = scale_for(xe_b).inv;
         sc->ain[0][q] = xe_b;
+        uint32_t bad = bound_bad(__uint_as_float(sc->bsync[BS_XE][q]));  // the bits: fmaxf drops a NaN
+        if (!fold) bad |= bound_bad(__uint_as_float(sc->bsync[BS_TE][q])) | bound_bad(__uint_as_float(sc->bsync[BS_TIN][q]));
+        sc->bad[q] = bad;
         if (!fold) {
             sc->ksc[G_TE / 4][q] = scale_for(__uint_as_float(sc->bsync[BS_TE][q])).inv;
             sc->ksc[G_TIN / 4][q] = scale_for(__uint_as_float(sc->bsync[BS_TIN][q])).inv;
@@ -425,9 +428,12 @@ __device__ __forceinline__ void fwd_block(const FwdArgs &a, h16x8 *lds, uint32_t
         const float4 b = sb[8 * 64 + kq];
         c1[0][0] = c1[0][0] * (a_inv(Ah) * ib1[0]) + f32x4{b.x, b.y, b.z, b.w};
         const int p = p0 + 16 * hq + col;
+        // a column tile with a bound the split cannot carry (bound_bad) is poisoned: NaN for all its points
+        const bool poison = sc->bad[hq] != 0;
 #pragma unroll
         for (int i = 0; i < 4; i++)
-            if (a.out && p < pend && 4 * kq + i < F.nout) a.out[(size_t)p * F.nout + 4 * kq + i] = c1[0][0][i];
+            if (a.out && p < pend && 4 * kq + i < F.nout)
+                a.out[(size_t)p * F.nout + 4 * kq + i] = poison ? __builtin_nanf("") : c1[0][0][i];
     }
     if constexpr (NT == 1) {
         DGS_STAMP(21);
