@@ -122,6 +122,10 @@ _SIGS = {
     # (F, C, H, W, what) / (F, C, H, W, img, gt, what, out, scratch, stream): deformgs/image_metrics.py
     "dgs_image_metrics_scratch_bytes": ([I, I, I, I, ctypes.c_uint], SZ),
     "dgs_image_metrics": ([I, I, I, I, P, P, ctypes.c_uint, P, P, P], I),
+    # () / (F, H, W) / (F, H, W, img, gt, weights, flags, out, taps, scratch, stream): deformgs/lpips.py
+    "dgs_lpips_weight_floats": ([], SZ),
+    "dgs_lpips_scratch_bytes": ([I, I, I], SZ),
+    "dgs_lpips": ([I, I, I, P, P, P, ctypes.c_uint, P, P, P, P], I),
     "dgs_adam_step": ([I, ctypes.POINTER(AdamTensor), ctypes.c_double, ctypes.c_double, ctypes.c_double, P], I),
     "dgs_select_rows": ([I, P, I, ctypes.POINTER(RowJob), P], I),
     "dgs_gaussian_inputs_forward": ([I, I] + [P] * 7 + [I] + [P] * 5 + [P], I),

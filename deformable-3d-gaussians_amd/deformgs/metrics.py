@@ -4,8 +4,14 @@ For every <MODEL>/test/ours_* directory: per-view and mean PSNR (loss.psnr) and 
 (8-bit RGB PNGs read with deformgs/png.py, scaled to [0, 1] as torchvision's to_tensor does), written to
 <MODEL>/results.json ({method: {"SSIM", "PSNR", "LPIPS"}}) and <MODEL>/per_view.json ({method: {metric:
 {file name: value}}}) in the reference's layout. SSIM is the fused HIP loss kernel's mean SSIM
-(dgs_l1_ssim_forward: the reference's 11x11 sigma-1.5 window). LPIPS is recorded as null: the lpips package
-and its VGG weights are not assumed to be present.
+(dgs_l1_ssim_forward: the reference's 11x11 sigma-1.5 window). LPIPS is recorded as null unless the two weight
+files are given: they are the user's to supply, and nothing here ships or fetches them.
+
+--lpips_vgg VGG16.pth --lpips_lin VGG_LIN.pth: fills "LPIPS" in both files with LPIPS-VGG (deformgs.lpips: the
+lpips package's net='vgg', version 0.1, on the [0, 1] images as the reference passes them) from torchvision's
+VGG16 state dict and the LPIPS linear-layer file: one batched call per group of equally sized images (at least
+16 pixels a side), the mean taken over the per-view values. --lpips_normalize maps the images through 2v - 1
+first. One of the two files without the other is an error.
 
 --ms_ssim: adds "MS-SSIM" (pytorch_msssim.ms_ssim's definition, data_range 1) and "D-SSIM" = (1 - MS-SSIM) / 2, the
 two further columns of the upstream Deformable-3D-Gaussians metrics.py, to both files: one batched
@@ -48,14 +54,13 @@ def read_images(renders_dir, gt_dir, device):
     return renders, gts, names
 
 
-def batched_ms_ssim(renders, gts):
-    """MS-SSIM of every (1, 3, H, W) pair: one image_metrics call per image size, one host read."""
-    from .image_metrics import image_metrics
+def by_size(renders, gts, score):
+    """score(renders, gts) -> (n,) device tensor, called once per group of equally sized (1, 3, H, W) pairs;
+    -> the values in the order of `renders`, read back after the last call."""
     groups = {}
     for i, r in enumerate(renders):
         groups.setdefault(tuple(r.shape), []).append(i)
-    parts = [(idx, image_metrics([renders[i] for i in idx], [gts[i] for i in idx], ("ms_ssim",))["ms_ssim"])
-             for idx in groups.values()]
+    parts = [(idx, score([renders[i] for i in idx], [gts[i] for i in idx])) for idx in groups.values()]
     values = [0.0] * len(renders)
     for idx, v in parts:
         for i, x in zip(idx, v.tolist()):
@@ -63,8 +68,21 @@ def batched_ms_ssim(renders, gts):
     return values
 
 
-def evaluate(model_paths, ssim_fn=None, device="cuda", ms_ssim=False):
-    """Writes results.json / per_view.json under every model path; -> {model path: results dict}."""
+def batched_ms_ssim(renders, gts):
+    """MS-SSIM of every (1, 3, H, W) pair: one image_metrics call per image size, one host read."""
+    from .image_metrics import image_metrics
+    return by_size(renders, gts, lambda r, g: image_metrics(r, g, ("ms_ssim",))["ms_ssim"])
+
+
+def batched_lpips(renders, gts, weights, normalize=False):
+    """LPIPS-VGG of every (1, 3, H, W) pair: one lpips call per image size, one host read."""
+    from .lpips import lpips
+    return by_size(renders, gts, lambda r, g: lpips(r, g, weights, normalize=normalize))
+
+
+def evaluate(model_paths, ssim_fn=None, device="cuda", ms_ssim=False, lpips_weights=None, lpips_normalize=False):
+    """Writes results.json / per_view.json under every model path; -> {model path: results dict}.
+    lpips_weights: deformgs.lpips weights on `device`, or None to record LPIPS as null."""
     ssim_fn = ssim_fn or fused_ssim
     full = {}
     for scene_dir in model_paths:
@@ -82,11 +100,17 @@ def evaluate(model_paths, ssim_fn=None, device="cuda", ms_ssim=False):
             m_ssim, m_psnr = torch.tensor(ssims).mean().item(), torch.tensor(psnrs).mean().item()
             print("  SSIM : {:>12.7f}".format(m_ssim))
             print("  PSNR : {:>12.7f}".format(m_psnr))
-            print("  LPIPS: not computed\n")
-            full[scene_dir][method] = {"SSIM": m_ssim, "PSNR": m_psnr, "LPIPS": None}
+            m_lpips, lpipss = None, [None] * len(names)
+            if lpips_weights is None:
+                print("  LPIPS: not computed\n")
+            else:
+                lp = torch.tensor(batched_lpips(renders, gts, lpips_weights, lpips_normalize))
+                m_lpips, lpipss = lp.mean().item(), lp.tolist()
+                print("  LPIPS: {:>12.7f}\n".format(m_lpips))
+            full[scene_dir][method] = {"SSIM": m_ssim, "PSNR": m_psnr, "LPIPS": m_lpips}
             per_view[method] = {"SSIM": dict(zip(names, torch.tensor(ssims).tolist())),
                                 "PSNR": dict(zip(names, torch.tensor(psnrs).tolist())),
-                                "LPIPS": {n: None for n in names}}
+                                "LPIPS": dict(zip(names, lpipss))}
             if ms_ssim:
                 ms = torch.tensor(batched_ms_ssim(renders, gts))
                 m_ms = ms.mean().item()
@@ -110,11 +134,24 @@ def build_parser():
     ap.add_argument("--ms_ssim", action="store_true",
                     help="also write MS-SSIM and D-SSIM = (1 - MS-SSIM) / 2 (images larger than 160 pixels a side)")
     ap.add_argument("--png", choices=["zlib", "gpu"], default="zlib", help="--synthetic: the PNG writer of the render step")
+    ap.add_argument("--lpips_vgg", metavar="VGG16.pth", help="torchvision's VGG16 state dict; with --lpips_lin: write LPIPS-VGG")
+    ap.add_argument("--lpips_lin", metavar="VGG_LIN.pth", help="the LPIPS linear-layer weights that go with --lpips_vgg")
+    ap.add_argument("--lpips_normalize", action="store_true", help="map the images through 2v - 1 before LPIPS")
     return ap
 
 
+def parse_args(argv=None):
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if bool(args.lpips_vgg) != bool(args.lpips_lin):
+        ap.error("--lpips_vgg and --lpips_lin go together: LPIPS-VGG needs both weight files")
+    if args.lpips_normalize and not args.lpips_vgg:
+        ap.error("--lpips_normalize needs --lpips_vgg and --lpips_lin")
+    return args
+
+
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     if args.synthetic:
         from . import render_cli
         for m in args.model_paths:
@@ -122,7 +159,11 @@ def main(argv=None):
             if not (os.path.isdir(t) and any(d.startswith("ours") for d in os.listdir(t))):
                 render_cli.main(["-m", m, "--synthetic", str(args.synthetic), "--res", str(args.res[0]), str(args.res[1]),
                                  "--mode", "render", "--skip_train", "--png", args.png])
-    return evaluate(args.model_paths, ms_ssim=args.ms_ssim)
+    weights = None
+    if args.lpips_vgg:
+        from .lpips import load_weights
+        weights = load_weights(args.lpips_vgg, args.lpips_lin, "cuda")
+    return evaluate(args.model_paths, ms_ssim=args.ms_ssim, lpips_weights=weights, lpips_normalize=args.lpips_normalize)
 
 
 if __name__ == "__main__":

@@ -290,6 +290,34 @@ size_t dgs_image_metrics_scratch_bytes(int F, int C, int H, int W, unsigned what
 int dgs_image_metrics(int F, int C, int H, int W, const float *img, const float *gt, unsigned what, float *out,
                       void *scratch, void *stream);
 
+/* ---- LPIPS-VGG, forward only (lpips.LPIPS(net='vgg'), version 0.1; csrc/lpips.hip) ----
+ * img, gt: (F,3,H,W) planar floats, taken as given ([0,1] as the reference's metrics.py passes them);
+ * DGS_LPIPS_NORMALIZE in flags maps both through 2v - 1 first. Per image: (v - shift) / scale with
+ * shift (-.030, -.088, -.188), scale (.458, .448, .450); the 13 convolutions of VGG16's feature stack (3x3,
+ * stride 1, zero padding 1, bias, ReLU; fp32 MFMA, fp32 accumulation) with 2x2 / stride 2 max pools (floor)
+ * after the 2nd, 4th, 7th and 10th; taps = the ReLU outputs before each pool and at the end (64, 128, 256,
+ * 512, 512 channels at H x W, H/2 x W/2, ... H/16 x W/16). Layer term k = mean over pixels of
+ * sum_c lin_k[c] (x_c / (|x| + 1e-10) - y_c / (|y| + 1e-10))^2. out (device): (F, 6) = the five layer terms,
+ * then their sum.
+ * weights (device): dgs_lpips_weight_floats() floats = for conv l = 0..12 its kernel packed as
+ * [Cin_p / 16][Cout][ky * 3 + kx][16] (element = W[co][16 i + j][ky][kx], Cin_p = Cin but 16 for the first
+ * layer, whose entries j >= 3 are zero) followed by its Cout biases; then lin_0 .. lin_4 (64, 128, 256,
+ * 512, 512 floats). deformgs/lpips.py packs them from the two standard state dicts.
+ * taps (device) or NULL: receives the five taps of img, one after the other, each as [F][Hk][Wk][Ck]
+ * floats (channel innermost): F * sum_k Hk Wk Ck floats.
+ * scratch: dgs_lpips_scratch_bytes(F, H, W) = F * dgs_lpips_scratch_bytes(1, H, W) bytes (two activation
+ * buffers of 2F * 64 H W floats and the tail's partial sums); 0 for sizes dgs_lpips rejects. 16-byte aligned.
+ * A fixed number of launches for any F, no host wait, no atomics: results are bitwise reproducible, a
+ * frame's result does not depend on the batch around it, equal images score exactly 0 and swapping img
+ * and gt changes no bit.
+ * DGS_ERR_ARGS: null pointer, non-positive size, min(H,W) < 16, unknown flag.
+ * DGS_ERR_UNSUPPORTED: F > 4095 or more than 2^30 pixels per image (score in chunks). */
+#define DGS_LPIPS_NORMALIZE 1u
+size_t dgs_lpips_weight_floats(void);
+size_t dgs_lpips_scratch_bytes(int F, int H, int W);
+int dgs_lpips(int F, int H, int W, const float *img, const float *gt, const float *weights, unsigned flags,
+              float *out, float *taps, void *scratch, void *stream);
+
 /* ---- simple-knn replacement: mean squared distance to the 3 nearest neighbours ---- */
 int dgs_knn_dist2(int P, const float *points, float *dist2, void *stream);
 
